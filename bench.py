@@ -31,6 +31,10 @@ Rank 0 prints ONE JSON line with the driver's contract plus
                      the live reference in the build container: profiles/r5_port_vs_reference.json) on the
                      configuration of ``value`` itself (cfg2, batch 256, 32 threads), with cfg1 (batch 16,
                      1 thread = what bm/train.py:182 configures, and 32 threads) as a sub-block.
+
+``--dump-outputs DIR`` writes what the last timed step left to its caller -- the loss and the model's state_dict --
+as ``DIR/<name>.npy`` (rank 0, float32 / float64, a seeded sample of the large arrays beyond 48 MB in all): the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -553,6 +557,41 @@ def pcie_inclusive_block(workload, B, dev, solver, steps, rank=0, n=4):
             "how": "pinned host batches, next batch staged on a copy stream during the step (Solver.stage / prefetch)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20        # below the 64 MB cap of --dump-outputs, .npy headers included
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step holds after its last step -- the loss it returned and the model's state_dict
+    (parameters after Adam, BatchNorm running statistics) -- written as `out_dir/<name>.npy` in float32 (integers in
+    float64).  When the state is larger than DUMP_BUDGET_BYTES, every array of more than 64 Ki elements is replaced by
+    the same fixed fraction of its elements at sorted positions drawn from a generator seeded with the array's name,
+    so that two builds write the same positions."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": loss.detach().float().cpu().numpy()}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        arrays[k] = (v.float() if v.is_floating_point() else v.double()).numpy()
+    big = [k for k, a in arrays.items() if a.size > 1 << 16]
+    small_bytes = sum(a.nbytes for k, a in arrays.items() if k not in big)
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - small_bytes) / big_bytes) if big_bytes else 1.0
+    sampled = []
+    if frac < 1.0:
+        for k in big:
+            a = arrays[k].reshape(-1)
+            gen = torch.Generator().manual_seed(zlib.crc32(k.encode()))
+            idx = torch.randperm(a.size, generator=gen)[:int(a.size * frac)].sort().values.numpy()
+            arrays[k] = a[idx]
+            sampled.append(k)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", a)
+    return {"dir": str(out_dir), "arrays": len(arrays), "bytes": sum(a.nbytes for a in arrays.values()),
+            "sampled_fraction": frac, "sampled": sampled}
+
+
 def flush_c_stdio():
     """librccl prints a version banner to the C-level stdout when the first communicator comes up; on a pipe that
     text sits in the stdio buffer until exit and would land BEHIND the JSON line.  Flushing right after init (every
@@ -658,7 +697,12 @@ def main():
     ap.add_argument("--dtype", default=hip_ops.DEFAULT_COMPUTE_DTYPE, choices=sorted(hip_ops.COMPUTE_DTYPES),
                     help="compute mode of the contractions; every fp32-class mode (f16x2, f32x3, f32) is held to the "
                          "same parity tolerances")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left to its caller (loss, state_dict) "
+                         "as DIR/<name>.npy (rank 0; a seeded sample of each large array beyond 48 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -713,6 +757,7 @@ def main():
         cur, nxt = stream.next()
         solver.train_step(cur, next_batch=nxt if prefetch else None)
     elapsed, loss = timed_steps(args.steps)
+    dumped = dump_outputs(args.dump_outputs, loss, model) if args.dump_outputs and rank == 0 else None
     final_loss = float(loss)
     if final_loss != final_loss or abs(final_loss) == float("inf"):
         # a throughput number of a diverged run is worthless (and flattering: the matrix pipe clocks higher on NaNs)
@@ -852,6 +897,7 @@ def main():
     # first real multi-GPU run needs to explain itself.  `cand_gather` runs on the side stream under the backward pass;
     # `gather_wait` is the part of it the compute stream actually waits for.
     out["comm_ms"] = comm_ms
+    out["dump_outputs"] = dumped
     out["comm_world_reported"] = distrib.reported_world()
     # one-pass BatchNorm backward: workgroups that gave up polling for a partner's sums and computed them themselves
     # (slow path, never wrong) since the process started -- 0 unless partners were not co-resident

@@ -21,7 +21,7 @@ HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE))
 sys.path.insert(0, str(HERE.parent.parent))
 
-from _ref_import import load_reference, load_reference_norm  # noqa: E402
+from _ref_import import REF, load_reference, load_reference_norm  # noqa: E402
 from brainmagick_amd.synthetic import make_batch  # noqa: E402
 
 SMALL = dict(C=20, T=48, F=10, S=5, B=6)
@@ -386,6 +386,60 @@ def mne_layout_fixture(common):
             "ch_names": np.array(ch_names), "positions": positions.numpy().copy()}
 
 
+# function -> {root expression (as source) -> role}: which local names / attributes of the reference's own code hold
+# the objects that brainmagick_amd replaces
+_CONTRACT_ROOTS = {
+    ("solver.py", "Solver._process_batch"): {"self.model": "model", "self.feature_model": "feature_model",
+                                             "self.scale_reject": "scale_reject", "batch": "batch"},
+    ("solver.py", "Solver._run_one_epoch"): {"self.model": "model", "self.loss": "loss", "self.optimizer": "optimizer",
+                                             "self.all_models": "module_list", "batch": "batch"},
+    ("solver.py", "Solver._create_loss"): {"loss": "loss", "self.optimizer": "optimizer", "ClipLoss": "loss_class"},
+    ("solver.py", "Solver.train"): {"self.scale_reject": "scale_reject"},
+    ("solver.py", "Solver.predict"): {"SegmentBatch": "batch_class"},
+    ("wer.py", "get_wer"): {"solver.model": "model", "solver.loss": "loss", "clip": "loss", "batch": "batch"},
+}
+
+
+def solver_contract_fixture():
+    """The reference Solver's contract, read from its source (nothing is imported: flashy / dora / julius are absent):
+    ``touches`` = {role: {attribute or "__call__": [[n positional, [keyword names], has **kwargs], ...]}} -- every
+    attribute the reference's hot loop reads on, and every call it makes to, the objects in _CONTRACT_ROOTS, by
+    walking the AST of bm/solver.py and bm/wer.py; ``clip_config`` = the `clip:` block of conf/config.yaml (the
+    keyword arguments of `ClipLoss(**args.clip, ...)`, bm/solver.py:85-88)."""
+    import ast
+    import yaml
+    ref_bm = REF / "bm"
+    touches = {}
+
+    def note(role, name, call=None):
+        calls = touches.setdefault(role, {}).setdefault(name, [])
+        if call is not None and call not in calls:
+            calls.append(call)
+
+    trees = {}
+    for (fname, qual), roots in _CONTRACT_ROOTS.items():
+        tree = trees.setdefault(fname, ast.parse((ref_bm / fname).read_text()))
+        node = tree
+        for part in qual.split("."):
+            node = next(n for n in ast.walk(node) if isinstance(n, (ast.ClassDef, ast.FunctionDef)) and n.name == part)
+        for n in ast.walk(node):
+            if isinstance(n, ast.Call):
+                src = ast.unparse(n.func)
+                sig = [len(n.args), sorted(k.arg for k in n.keywords if k.arg), any(k.arg is None for k in n.keywords)]
+                if src in roots:
+                    note(roots[src], "__call__", sig)
+                elif isinstance(n.func, ast.Attribute) and ast.unparse(n.func.value) in roots:
+                    note(roots[ast.unparse(n.func.value)], n.func.attr, sig)
+            elif isinstance(n, ast.Attribute) and ast.unparse(n.value) in roots:
+                note(roots[ast.unparse(n.value)], n.attr)
+        # len(batch...) / `if self.scale_reject:` style uses
+        for n in ast.walk(node):
+            if isinstance(n, ast.Call) and ast.unparse(n.func) == "len" and n.args and ast.unparse(n.args[0]) in roots:
+                note(roots[ast.unparse(n.args[0])], "__len__")
+    clip_config = yaml.safe_load((ref_bm / "conf" / "config.yaml").read_text())["clip"]
+    return {"touches": touches, "clip_config": clip_config}
+
+
 def wide_kernels_fixture(sc, common, losses):
     """The paper architecture at the smallest size the headline wide f16x2 kernels take (hidden 256, depth 4, 64
     sensors, T = 192, batch 8), two training steps of the live reference.  Parameters (1.6 M) and inputs are rebuilt
@@ -487,6 +541,8 @@ def main(only=()):
     print("retrieval_rules: done")
     np.savez_compressed(HERE / "mne_layout.npz", **mne_layout_fixture(common))
     print("mne_layout: done")
+    (HERE / "solver_contract.json").write_text(json.dumps(solver_contract_fixture(), indent=1) + "\n")
+    print("solver_contract: done")
 
 
 if __name__ == "__main__":

@@ -716,62 +716,19 @@ def test_header_prototypes_match_the_definitions():
     assert r.returncode == 0, r.stderr[:2000]
 
 
-# -- the reference Solver's contract, read from its source ----------------------------------------------------------
-REFERENCE_BM = Path("/root/reference/bm")
-
-# function -> {root expression (as source) -> role}: which local names / attributes of the reference's own code hold
-# the objects that brainmagick_amd replaces
-_CONTRACT_ROOTS = {
-    ("solver.py", "Solver._process_batch"): {"self.model": "model", "self.feature_model": "feature_model",
-                                             "self.scale_reject": "scale_reject", "batch": "batch"},
-    ("solver.py", "Solver._run_one_epoch"): {"self.model": "model", "self.loss": "loss", "self.optimizer": "optimizer",
-                                             "self.all_models": "module_list", "batch": "batch"},
-    ("solver.py", "Solver._create_loss"): {"loss": "loss", "self.optimizer": "optimizer", "ClipLoss": "loss_class"},
-    ("solver.py", "Solver.train"): {"self.scale_reject": "scale_reject"},
-    ("solver.py", "Solver.predict"): {"SegmentBatch": "batch_class"},
-    ("wer.py", "get_wer"): {"solver.model": "model", "solver.loss": "loss", "clip": "loss", "batch": "batch"},
-}
+# -- the reference Solver's contract, read from its source by tests/golden/make_golden.py ----------------------------
+def _reference_contract():
+    """(touches, clip_config) of tests/golden/solver_contract.json: {role: {attribute or "__call__": [(n positional,
+    (keyword names), has **kwargs)]}} -- every attribute the reference's hot loop reads on, and every call it makes to,
+    the objects the replacement classes stand for -- and the `clip:` block of the reference's conf/config.yaml."""
+    import json
+    from helpers import GOLDEN
+    data = json.loads((GOLDEN / "solver_contract.json").read_text())
+    touches = {role: {name: [(c[0], tuple(c[1]), c[2]) for c in calls] for name, calls in attrs.items()}
+               for role, attrs in data["touches"].items()}
+    return touches, data["clip_config"]
 
 
-def _reference_touches():
-    """{role: {attribute or "__call__": [(n positional, (keyword names))]}} -- every attribute the reference's hot
-    loop reads on, and every call it makes to, the objects in _CONTRACT_ROOTS, by walking the AST of the reference
-    sources (nothing is imported: flashy / dora / julius are absent from this image)."""
-    import ast
-    touches = {}
-
-    def note(role, name, call=None):
-        calls = touches.setdefault(role, {}).setdefault(name, [])
-        if call is not None and call not in calls:
-            calls.append(call)
-
-    trees = {}
-    for (fname, qual), roots in _CONTRACT_ROOTS.items():
-        tree = trees.setdefault(fname, ast.parse((REFERENCE_BM / fname).read_text()))
-        node = tree
-        for part in qual.split("."):
-            node = next(n for n in ast.walk(node) if isinstance(n, (ast.ClassDef, ast.FunctionDef)) and n.name == part)
-        for n in ast.walk(node):
-            if isinstance(n, ast.Call):
-                src = ast.unparse(n.func)
-                sig = (len(n.args), tuple(sorted(k.arg for k in n.keywords if k.arg)),
-                       any(k.arg is None for k in n.keywords))
-                if src in roots:
-                    note(roots[src], "__call__", sig)
-                elif isinstance(n.func, ast.Attribute) and ast.unparse(n.func.value) in roots:
-                    note(roots[ast.unparse(n.func.value)], n.func.attr, sig)
-            elif isinstance(n, ast.Attribute) and ast.unparse(n.value) in roots:
-                note(roots[ast.unparse(n.value)], n.attr)
-            elif isinstance(n, ast.Call) is False and isinstance(n, ast.Name) and False:
-                pass
-        # len(batch...) / `if self.scale_reject:` style uses
-        for n in ast.walk(node):
-            if isinstance(n, ast.Call) and ast.unparse(n.func) == "len" and n.args and ast.unparse(n.args[0]) in roots:
-                note(roots[ast.unparse(n.args[0])], "__len__")
-    return touches
-
-
-@pytest.mark.skipif(not REFERENCE_BM.exists(), reason="needs the reference checkout (build container only)")
 def test_reference_solver_contract_is_met_by_the_replacement_classes():
     """INTEGRATION.md section 4 says the maintainer changes imports and one factory line and `bm/solver.py` /
     `bm/wer.py` stay as they are.  flashy / dora are absent, so the reference Solver cannot RUN here; this is the next
@@ -784,8 +741,8 @@ def test_reference_solver_contract_is_met_by_the_replacement_classes():
     from brainmagick_amd.losses import ClipLoss
     from brainmagick_amd.norm import ScaleReject
     from brainmagick_amd.optim import FlatAdam
-    touches = _reference_touches()
-    # the walk found the calls the hot loop is made of (a reference that moved would fail here, not pass vacuously)
+    touches, clip_cfg = _reference_contract()
+    # the fixture holds the calls the hot loop is made of (a walk of a reference that moved fails here, not vacuously)
     assert (2, (), False) in touches["model"]["__call__"]                     # self.model(inputs, batch)
     assert "modules" in touches["model"] and "eval" in touches["model"]
     assert (3, (), False) in touches["loss"]["__call__"]                      # self.loss(estimate, output, features_mask)
@@ -840,8 +797,6 @@ def test_reference_solver_contract_is_met_by_the_replacement_classes():
                     bind(member, sig, f"{role}.{name}(...)")
     # `ClipLoss(**args.clip, dset_args=args.dset)` (bm/solver.py:85-88): every key of conf/config.yaml's `clip:` block
     # minus the two the Solver pops must be a constructor argument
-    import yaml
-    clip_cfg = yaml.safe_load((REFERENCE_BM / "conf" / "config.yaml").read_text())["clip"]
     kw = {k: v for k, v in clip_cfg.items() if k not in ("save_best", "sync_grad")}
     inspect.signature(ClipLoss).bind(**kw, dset_args=None)
     # SegmentBatch(meg, features, mask, subjects, recordings) positionally (bm/solver.py `predict`)
@@ -876,12 +831,41 @@ def test_bench_reads_the_counter_passes_like_the_guide_prescribes(tmp_path):
     assert step_bytes == pytest.approx(per_launch * 4)
 
 
-def test_comm_timer_is_inert_without_a_gpu_and_names_the_phases():
+def test_bench_dump_outputs_writes_the_loss_and_the_state_within_the_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the loss and every state_dict entry as DIR/<name>.npy in float32 / float64, whole
+    while they fit the budget; beyond it, the large arrays are sampled at positions that do not change between runs."""
+    import numpy as np
+    import bench
+    from brainmagick_amd.models import SimpleConv
+    torch.manual_seed(0)
+    model = SimpleConv(in_channels={"meg": 6}, out_channels=4, hidden={"meg": 8}, n_subjects=2, depth=2,
+                       merger=True, merger_pos_dim=2048, merger_channels=270, subject_layers=False)
+    sd = model.state_dict()
+    assert sd["merger.heads"].numel() > 1 << 16
+    loss = torch.tensor(2.5)
+    info = bench.dump_outputs(tmp_path / "whole", loss, model)
+    assert info["sampled"] == [] and info["arrays"] == len(sd) + 1
+    assert np.load(tmp_path / "whole" / "loss.npy") == np.float32(2.5)
+    for k, v in sd.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == (np.float32 if v.is_floating_point() else np.float64), k
+        assert np.array_equal(a, v.double().numpy()), k
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    runs = [bench.dump_outputs(tmp_path / f"sampled{i}", loss, model) for i in range(2)]
+    assert runs[0]["sampled"] == ["merger.heads"] and runs[0]["bytes"] <= 1 << 20
+    a, b = (np.load(tmp_path / f"sampled{i}" / "merger.heads.npy") for i in range(2))
+    assert a.dtype == np.float32 and 0 < a.size < sd["merger.heads"].numel() and np.array_equal(a, b)
+    assert np.isin(a, sd["merger.heads"].numpy()).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "sampled0").iterdir()) <= 64e6
+
+
+def test_comm_timer_is_inert_without_a_gpu_and_names_the_phases(monkeypatch):
     from brainmagick_amd import distrib
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)     # the same check on a machine that has a GPU
     t = distrib.CommTimer()
     distrib.set_comm_timer(t)
     try:
-        with distrib._phase("reduce_scatter"):       # no GPU here: a null context, nothing recorded
+        with distrib._phase("reduce_scatter"):       # no GPU: a null context, nothing recorded
             pass
         assert t.records == [] and t.summary(3) == {}
     finally:

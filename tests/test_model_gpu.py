@@ -8,7 +8,8 @@ import os
 import pytest
 import torch
 
-from helpers import Golden, MODEL_FIXTURES, OFF_PATH_FIXTURES, rel_l2
+from helpers import (Golden, MODEL_FIXTURES, OFF_PATH_FIXTURES, adam_params_close, close, is_noise_grad, rel_l2,
+                     running_stat_close)
 from oracle import bm_oracle as O
 from brainmagick_amd import synthetic
 
@@ -19,55 +20,7 @@ GRAD_TOL = 1e-4
 LOSS_TOL = 1e-4
 
 
-NOISE = 1e-6
 PARITY_NOISE = 2.5      # planted-noise level of the long-horizon parity run (calibrated: top-10 far from 0 % and 100 %)
-
-
-def close(a, b, tol, ref_scale):
-    """rel-L2 <= tol.  The only escape is for gradients that are round-off noise IN THE REFERENCE (analytically zero:
-    the conv bias in front of a BatchNorm has sum(dy) == 0; recognised by max|g_ref| <= 1e-5 x the largest gradient
-    norm of the model): there max|a-b| <= 1e-6 x that norm.  A parameter with a small but genuine gradient gets no
-    absolute escape -- it has to meet the relative tolerance on its own norm."""
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    if (a - b).norm().item() <= tol * b.norm().item():
-        return True
-    return is_noise_grad(b, ref_scale) and (a - b).abs().max().item() <= NOISE * ref_scale
-
-
-def is_noise_grad(g, ref_scale):
-    """Adam turns a round-off-noise gradient into a full +-lr update (g / (|g| + eps)), so the
-    parameters behind such gradients are not reproducible across implementations (nor across
-    BLAS/thread counts of the reference itself); they are excluded from after-step comparisons."""
-    return g.abs().max().item() <= 10 * NOISE * ref_scale
-
-
-def adam_params_close(p, p_ref, nsteps, g_ref=None, gscale=1.0, lr=3e-4):
-    """After-step parameter check that is robust to Adam's sign amplification: at step 1 the update
-    is lr * g / (|g| + eps) = +-lr whatever |g|, so an element whose gradient is round-off noise
-    around 0 may legitimately move by +lr in one implementation and -lr in the other (sensor-attention
-    heads have thousands of such near-cancelling entries).  Required: >= 99 % of the elements agree
-    to 1e-6 absolute (a wrong lr / beta / bias-correction would move ALL of them) and nothing differs
-    by more than the 2*lr*nsteps a sign flip can produce.  The tight checks are the per-step losses
-    (step k+1's loss sees step k's update), the step-0 gradients and test_adam_kernel (bitwise-close
-    Adam arithmetic given identical gradients)."""
-    d = (p.detach().double().cpu() - p_ref.detach().double().cpu()).abs()
-    bad = d > 1e-6
-    if g_ref is not None:
-        # elements whose reference gradient is itself round-off noise (e.g. the k=0 cosine column of
-        # the attention heads: sum_c dsoftmax == 0) are not counted
-        bad &= g_ref.detach().double().cpu().abs() > 10 * NOISE * gscale
-    frac_bad = bad.double().mean().item()
-    return frac_bad <= 1e-2 and d.max().item() <= 2.1 * lr * nsteps, (frac_bad, d.max().item())
-
-
-def running_stat_close(v, v_ref, nsteps, lr=3e-4, momentum=0.1):
-    """BatchNorm running statistics: tight (2e-5 rel-L2) after one step; from the second step on the
-    batch mean absorbs the noise-driven +-lr drift of the conv bias in front of the BatchNorm (see
-    is_noise_grad), i.e. up to momentum * 2*lr per extra step in absolute terms."""
-    if rel_l2(v, v_ref) < 2e-5:
-        return True
-    d = (v.detach().double().cpu() - v_ref.detach().double().cpu()).abs().max().item()
-    return d <= 2.1 * lr * momentum * (nsteps - 1) + 1e-6
 
 
 class _Batch:
@@ -954,6 +907,33 @@ def test_bench_under_a_launcher_prints_one_json_line_and_nothing_else():
     line = json.loads(lines[0])
     assert line["config"]["comm"] == "rccl/c-abi" and line["config"]["rccl_world"] == 1
     assert line["config"]["negatives"] == "node" and line["value"] > 0
+
+
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the loss of the last timed step (the one the result line reports) and
+    the model state it left, in float32 / float64 and within 64 MB; `--steps` is the number of timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parent.parent
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "BM_FORCE_DISTRIBUTED"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path), "--no-cpu-baseline", "--accuracy-steps", "0", "--no-exact",
+                          "--no-clip", "--no-side-blocks", "--no-pmc"], env=env, capture_output=True, text=True,
+                         timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert float(np.load(tmp_path / "loss.npy")) == line["config"]["final_loss"]
+    files = sorted(tmp_path.glob("*.npy"))
+    assert len(files) == line["dump_outputs"]["arrays"] and sum(f.stat().st_size for f in files) <= 64e6
+    heads = np.load(tmp_path / "merger.heads.npy")
+    assert heads.dtype == np.float32 and np.isfinite(heads).all()
 
 
 # Dimensions of the long-horizon parity runs (this test and bench.py's `retrieval_parity`): every contraction of the

@@ -3,7 +3,7 @@ import pytest
 import torch
 
 from oracle import bm_oracle as O
-from helpers import Golden, MODEL_FIXTURES, rel_l2
+from helpers import NOISE, Golden, MODEL_FIXTURES, close, rel_l2, running_stat_close
 
 # fp32 oracle vs fp32 reference: same torch kernels in (nearly) the same order
 FWD_TOL = 2e-6
@@ -19,6 +19,9 @@ def test_oracle_matches_reference(name):
     model = O.OracleModel(sd0, meta["cfg"], meta["hidden"], meta["F"])
     training = meta["training"]
     if training and meta["n_steps"]:
+        # the conv biases in front of a BatchNorm have analytically zero gradients: their round-off noise depends on the
+        # host's summation order (core count), so they are held to the noise rule of helpers.close / is_noise_grad
+        gscale = max(v.double().norm().item() for v in grads.values())
         losses = []
         for step in range(meta["n_steps"]):
             loss, est, gr = model.train_step(inp["meg"], inp["positions"], inp["subjects"],
@@ -28,11 +31,21 @@ def test_oracle_matches_reference(name):
                 assert rel_l2(est, g.t("out/estimate")) < FWD_TOL
                 assert set(gr) == set(grads)
                 for k in grads:
-                    assert rel_l2(gr[k], grads[k]) < GRAD_TOL, k
+                    assert close(gr[k], grads[k], GRAD_TOL, gscale), (k, rel_l2(gr[k], grads[k]))
         ref_losses = g.raw["out/losses"]
         assert max(abs(a - b) for a, b in zip(losses, ref_losses)) < 1e-5
         for k, v in sd1.items():
-            if v.is_floating_point():
+            if k in grads:
+                # Adam moves an element with a round-off-noise gradient by +-lr whatever its size (helpers.is_noise_grad):
+                # those elements are held to the sign-flip bound, all others to the tolerance
+                noise = grads[k].abs() <= 10 * NOISE * gscale
+                d = (model.sd[k].double() - v.double()).abs()
+                assert not noise.any() or d[noise].max() <= 2.1 * 3e-4 * meta["n_steps"], k
+                assert rel_l2(model.sd[k][~noise], v[~noise]) < 1e-5, k
+            elif k.endswith("running_mean") and meta["n_steps"] > 1:
+                # from the second step on, the batch mean carries that +-lr drift of the conv bias before the BatchNorm
+                assert running_stat_close(model.sd[k], v, meta["n_steps"]), k
+            elif v.is_floating_point():
                 assert rel_l2(model.sd[k], v) < 1e-5, k
             else:
                 assert int(model.sd[k]) == int(v), k
