@@ -491,3 +491,29 @@ def clip_forward_timed(estimate, candidate, inv, timer):
         return H.clip_ce(part, inv, want_grad=True, want_loss=True)
     finally:
         H.set_kernel_timer(None)
+
+
+class MaskedRegressionFn(torch.autograd.Function):
+    """L1Loss / L2Loss.forward (bm/losses.py:11-26): torch.nn.L1Loss() / MSELoss() over est[mask.expand_as(est)],
+    one forward and one backward launch (csrc/regress.hip).  ``mask`` None = all true; the count of selected elements
+    stays on the device, and the backward reads it and the incoming gradient there (no host sync).  ``flag`` (int32
+    device tensor, nullable) receives the "no mask!" bit when nothing is selected."""
+
+    @staticmethod
+    def forward(ctx, estimate, output, mask, kind: str, flag=None):
+        estimate, output = _c(estimate), _c(output)
+        mask = None if mask is None else _c(mask)
+        loss, count = H.regress_loss_fwd(estimate, output, mask, kind, flag)
+        ctx.kind = kind
+        ctx.save_for_backward(estimate, output, mask, count)
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    def backward(ctx, dloss, _dcount):
+        estimate, output, mask, count = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None, None
+        dest, dout = H.regress_loss_bwd(estimate, output, mask, ctx.kind, _c(dloss), count,
+                                        want_dout=ctx.needs_input_grad[1])
+        return (dest if ctx.needs_input_grad[0] else None), dout, None, None, None

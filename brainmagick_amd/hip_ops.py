@@ -822,6 +822,104 @@ def flag_unless_all_set(mask: torch.Tensor, flag: torch.Tensor) -> None:
           "bm_flag_unless_all_set")
 
 
+# ------------------------------------------------------------------------------------------------
+# Regression objective (csrc/regress.hip): L1Loss / L2Loss forward + backward, the test metrics' accumulators.
+REGRESS_KINDS = {"l1": 0, "mse": 1}
+METRIC_PLANES = 8          # sum l r m, sum l m, sum r m, sum (l m)^2, sum (r m)^2, sum m, sum ((l-r) m)^2, sum |(l-r) m|
+NO_MASK_BIT = 2            # flag word slot 2: "no mask!" (bm/solver.py:354-356); bit 1 there is ClipLoss' mask assert
+_regress_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
+
+
+def _regress_ws(device) -> torch.Tensor:
+    """Partials + ticket counters of the regression kernels: one ZEROED buffer per (device, stream); every launch
+    leaves its counter at zero again."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _regress_workspaces.get(key)
+    if ws is None:
+        ws = _regress_workspaces[key] = torch.zeros(lib().bm_regress_workspace_bytes(), device=device,
+                                                    dtype=torch.uint8)
+    return ws
+
+
+def _regress_mask(mask: tp.Optional[torch.Tensor], shape, what: str):
+    """(mask | None, mask mode): None = all true, 1 = [B, 1, T] broadcast over F, 2 = [B, F, T]."""
+    if mask is None:
+        return None, 0
+    _req(mask, f"{what}.mask", torch.bool)
+    B, F, T = shape
+    if tuple(mask.shape) == (B, 1, T):
+        return mask, 1
+    if tuple(mask.shape) == (B, F, T):
+        return mask, 2
+    raise BmHipError(f"{what}: mask of shape {tuple(mask.shape)} is neither [B, 1, T] nor [B, F, T] for {tuple(shape)}")
+
+
+def regress_loss_fwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[torch.Tensor], kind: str,
+                     flag: tp.Optional[torch.Tensor] = None):
+    """(loss [] fp32, count [] fp64) of L1 / MSE over the selected elements, device side, no sync.  ``flag`` (int32
+    device tensor, nullable): element 0 gets NO_MASK_BIT when nothing is selected (the loss is then NaN)."""
+    _req(est, "regress_loss.est")
+    _req(out, "regress_loss.out")
+    if est.dim() != 3 or out.shape != est.shape:
+        raise BmHipError(f"regress_loss: est {tuple(est.shape)} and out {tuple(out.shape)} must be the same [B, F, T]")
+    mask, mode = _regress_mask(mask, est.shape, "regress_loss")
+    B, F, T = est.shape
+    loss = torch.empty((), device=est.device, dtype=torch.float32)
+    count = torch.empty((), device=est.device, dtype=torch.float64)
+    ws = _regress_ws(est.device)
+    check(lib().bm_regress_loss_fwd(_p(est), _p(out), _p(mask), mode, B, F, T, REGRESS_KINDS[kind], _p(loss),
+                                    _p(count), _p(ws), ws.numel(), _p(_opt(flag, "flag", torch.int32)), _stream()),
+          "bm_regress_loss_fwd")
+    return loss, count
+
+
+def regress_loss_bwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[torch.Tensor], kind: str,
+                     grad_out: torch.Tensor, count: torch.Tensor, want_dout: bool = False):
+    """(dEst, dOut | None).  In f16x2 mode dEst carries its maximum and per-channel maxima (published by the same
+    launch) for the head's backward contractions."""
+    _req(est, "regress_loss_bwd.est")
+    _req(out, "regress_loss_bwd.out")
+    mask, mode = _regress_mask(mask, est.shape, "regress_loss_bwd")
+    B, F, T = est.shape
+    dest = torch.empty_like(est)
+    dout = torch.empty_like(out) if want_dout else None
+    slot = _amax_slot(dest)
+    ws = _regress_ws(est.device)
+    check(lib().bm_regress_loss_bwd(_p(est), _p(out), _p(mask), mode, B, F, T, REGRESS_KINDS[kind],
+                                    _p(_req(grad_out, "grad_out")), _p(_req(count, "count", torch.float64)),
+                                    _p(dest), _p(dout), _p(slot), _p(_row_amax_out(dest, slot)), _p(ws), ws.numel(),
+                                    _stream()), "bm_regress_loss_bwd")
+    return dest, dout
+
+
+def regress_metric_update(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[torch.Tensor], acc: torch.Tensor,
+                          t0: int = 0) -> torch.Tensor:
+    """acc [METRIC_PLANES, F, T - t0] fp64 += the per-(f, t) sums over the batch of est / out [B, F, T] (fp32; a channel
+    slice of a contiguous tensor is read in place), columns t >= t0 only.  mask: bool [B, 1, T] or [B, F, T], or None."""
+    for t, n in ((est, "est"), (out, "out")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _req(t, f"regress_metric_update.{n}")
+        if t.dtype != torch.float32:
+            raise BmHipError(f"regress_metric_update.{n}: expected dtype torch.float32, got {t.dtype}")
+    if est.dim() != 3 or out.shape != est.shape:
+        raise BmHipError(f"regress_metric_update: est {tuple(est.shape)} / out {tuple(out.shape)}: same [B, F, T]")
+    B, F, T = est.shape
+    # rows T apart, channels contiguous: a channel slice of a [B, F', T] tensor keeps its segment stride
+    est = est if est.stride()[1:] == (T, 1) else est.contiguous()
+    out = out if out.stride()[1:] == (T, 1) else out.contiguous()
+    if mask is not None:
+        if not mask.is_contiguous():
+            mask = mask.contiguous()
+    mask, mode = _regress_mask(mask, est.shape, "regress_metric_update")
+    _req(acc, "regress_metric_update.acc", torch.float64)
+    if not 0 <= t0 < T or tuple(acc.shape) != (METRIC_PLANES, F, T - t0):
+        raise BmHipError(f"regress_metric_update: acc {tuple(acc.shape)} / t0 {t0} for {tuple(est.shape)}")
+    check(lib().bm_regress_metric_update(_p(est), est.stride(0), _p(out), out.stride(0), _p(mask),
+                                         mask[0].numel() if mask is not None else 0, int(mode == 2), B, F, T, t0,
+                                         _p(acc), _stream()), "bm_regress_metric_update")
+    return acc
+
+
 def clip_ce(part, inv_norm, want_probs=False, want_grad=False, want_loss=False,
             target_offset: int = 0, col_valid: tp.Optional[torch.Tensor] = None):
     """part [nsplit][B][B'] -> (scores, probs|None, dscaled|None, loss|None).  ``col_valid`` ([B'] fp32, optional):

@@ -130,3 +130,52 @@ class ClipLoss(torch.nn.Module):
         scaled = (targets * inv.view(-1, 1, 1)).contiguous()
         cols = BF.ClipLossFn.apply(scaled, est_all, target_offset, None, False, False)[0]
         return 0.5 * (rows + cols)
+
+
+class _MaskedLoss(torch.nn.Module):
+    """bm/losses.py:11-14: the loss over ``estimate[mask.expand_as(estimate)]`` -- here without the gather: the kernels
+    read the mask in place ([B, 1, T] or [B, F, T] bool).  ``mask=None`` means all true (an extension: the reference
+    would fail on None)."""
+    kind = ""
+
+    def __init__(self):
+        super().__init__()
+        self.no_mask_flag = None    # Solver: int32 device word that receives the "no mask!" bit (bm/solver.py:354-356)
+
+    def forward(self, estimate, output, mask=None):
+        if not (estimate.is_cuda and output.is_cuda):
+            raise RuntimeError(f"brainmagick_amd.{type(self).__name__} runs on the MI355X HIP path only "
+                               "(no CPU fallback)")
+        if mask is not None:
+            if mask.dtype != torch.bool:
+                raise TypeError(f"mask must be a bool tensor (the reference indexes with it), got {mask.dtype}")
+            mask.expand_as(estimate)       # the reference's shape rule: broadcastable to the estimate
+        return BF.MaskedRegressionFn.apply(estimate, output, mask, self.kind, self.no_mask_flag)[0]
+
+
+class L1Loss(_MaskedLoss):
+    """torch.nn.L1Loss() over the selected elements (bm/losses.py:17-20)."""
+    kind = "l1"
+
+
+class L2Loss(_MaskedLoss):
+    """torch.nn.MSELoss() over the selected elements (bm/losses.py:23-26)."""
+    kind = "mse"
+
+
+def create_loss(name: str, **clip_kw) -> torch.nn.Module:
+    """The loss factory of bm/solver.py:76-94 (`optim.loss`): 'l1', 'mse' or 'clip' (``clip_kw`` = the `clip:`
+    configuration block, plus ``dset_args``)."""
+    if name == "l1":
+        return L1Loss()
+    if name == "mse":
+        return L2Loss()
+    if name == "clip":
+        kw = dict(clip_kw)
+        kw.pop("save_best", None)
+        kw.pop("sync_grad", None)
+        return ClipLoss(**kw)
+    if name == "regression_classification":
+        raise NotImplementedError("optim.loss='regression_classification' (FeatureDecodingLoss, categorical features) "
+                                  "is not part of brainmagick_amd")
+    raise ValueError(f"Unsupported loss {name}")

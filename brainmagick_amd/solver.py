@@ -1,7 +1,8 @@
 """Host-side mirror of the hot loop of ``bm/solver.py``: ``_process_batch`` (bm/solver.py:230-321)
 and the per-batch body of ``_run_one_epoch`` (bm/solver.py:343-390), for the decode task with the
-CLIP loss -- the path BASELINE.json names.  Everything around it in the reference (flashy stages,
-checkpoint commit, tensorboard, dataset construction) stays the reference's business.
+CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80).
+Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
+construction) stays the reference's business.
 
 Differences to the reference, all MI355X-motivated and opt-in/neutral:
   * gradients / optimizer: ONE flat bucket -> reduce-scatter + fused Adam on the shard + all-gather
@@ -16,23 +17,38 @@ import torch
 
 from . import distrib
 from . import hip_ops as H
-from .losses import ClipLoss
+from .losses import ClipLoss, _MaskedLoss
 from .optim import FlatAdam
 
 
 class Solver:
-    def __init__(self, model: torch.nn.Module, loss: tp.Optional[ClipLoss] = None,
+    def __init__(self, model: torch.nn.Module, loss: tp.Optional[tp.Union[ClipLoss, _MaskedLoss]] = None,
                  optimizer: tp.Optional[FlatAdam] = None, device: str = "cuda",
                  offset_meg_ms: float = 0., sample_rate: float = 120., negatives: str = "local",
                  lr: float = 3e-4, betas=(0.9, 0.999), scale_reject=None,
                  feature_model: tp.Optional[torch.nn.Module] = None, check_finite: bool = True,
                  n_negatives: tp.Optional[int] = None, negative_pool_size: tp.Optional[int] = None,
-                 batch_size: tp.Optional[int] = None):
+                 batch_size: tp.Optional[int] = None, mask_loss: bool = False):
         """``batch_size``: the configured per-rank batch size (`optim.batch_size` / world size, bm/train.py:37-39).
         Only whole-node negatives next to per-rank rejection need it: it is the block every rank contributes to the
         candidate all-gather.  Without it the block is the local batch's length and is verified over the ranks each
-        step (one tiny all-reduce + read-back; that mode reads back its rejection count anyway)."""
+        step (one tiny all-reduce + read-back; that mode reads back its rejection count anyway).
+
+        ``loss``: ``ClipLoss()`` (default), ``L1Loss()`` or ``L2Loss()`` (`optim.loss`, ``losses.create_loss``).
+        ``mask_loss`` (`task.mask_loss`, bm/solver.py:251-253) applies to the regression losses: False hands them
+        ``mask=None`` (all true, what the reference's ``torch.ones_like`` means, without the tensor), True the batch's
+        ``features_mask`` after the offset slice.  ClipLoss keeps receiving the batch's mask (it asserts it is all
+        true)."""
         assert negatives in ("local", "node")
+        self.regression = isinstance(loss, _MaskedLoss)
+        if self.regression:
+            if n_negatives is not None:          # bm/solver.py:362: `assert self.args.optim.loss == 'clip'`
+                raise ValueError("n_negatives (bm optim.negatives) completes the CLIP candidates; it does not apply to "
+                                 f"{type(loss).__name__}")
+            if negatives == "node":
+                raise ValueError(f'negatives="node" gathers CLIP candidates; {type(loss).__name__} has none: use '
+                                 'negatives="local"')
+        self.mask_loss = mask_loss
         self.batch_size = batch_size
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None and torch.cuda.is_available():
@@ -77,7 +93,12 @@ class Solver:
         # flashy.distrib.sync_model also averages the float buffers (BatchNorm running statistics)
         self._buffers = distrib.BufferBucket(self._all_models())
         self.check_finite = check_finite          # bm/solver.py:258-260 asserts (one fused host sync)
-        self.loss.defer_mask_check = check_finite  # bm/losses.py:110 assert: same sync point, one step late
+        if self.regression:
+            # bm/solver.py:354-356 "no mask!": the loss' forward kernel raises a bit of the flag word, read at the same
+            # sync point (without check_finite: a synchronising assert, see _loss_mask)
+            self.loss.no_mask_flag = H.index_error_flag(self.device)[2:3] if check_finite else None
+        else:
+            self.loss.defer_mask_check = check_finite  # bm/losses.py:110 assert: same sync point, one step late
         self._last_batch = None
         self._prefetched = None
         self._staged: tp.Dict[int, tuple] = {}    # id(host batch) -> (host batch, device batch): see stage()
@@ -151,8 +172,11 @@ class Solver:
             flag = H.index_error_flag(meg.device)
             if meg.is_contiguous() and features.is_contiguous() and meg.dtype == features.dtype == torch.float32:
                 H.amax(meg, nonfinite_flag=flag[1:2])
-                # candidates: norms, maximum and finiteness in one pass (ClipLoss finds them on the tensor)
-                H.clip_inv_norms(features, nonfinite_flag=flag[1:2])
+                if self.regression:
+                    H.amax(features, nonfinite_flag=flag[1:2])      # (regression needs no candidate norms)
+                else:
+                    # candidates: norms, maximum and finiteness in one pass (ClipLoss finds them on the tensor)
+                    H.clip_inv_norms(features, nonfinite_flag=flag[1:2])
             else:
                 finite = torch.isfinite(meg).all() & torch.isfinite(features).all()
                 flag[1:2].bitwise_or_((~finite).to(torch.int32).view(1))
@@ -232,6 +256,9 @@ class Solver:
         if nonfinite:
             flag[1:2].zero_()
             raise AssertionError("non-finite values in the MEG or feature tensors")
+        if bad_mask & H.NO_MASK_BIT:
+            flag[2:3].zero_()
+            raise AssertionError("no mask! (bm/solver.py:354-356: the loss mask selects no element)")
         if bad_mask:
             flag[2:3].zero_()
             raise AssertionError("mask is not supported for now (bm/losses.py:110; reported one step late)")
@@ -261,7 +288,9 @@ class Solver:
         if prepared is None:
             return None, None, None, None
         if defer_flags:
-            self._flag_ticket = self._post_flags()
+            # (a regression loss raises its "no mask!" bit in its own forward kernel: train_step posts the read behind it)
+            if not self.regression:
+                self._flag_ticket = self._post_flags()
         else:
             self._check_flags()
         batch, meg, features, features_mask, reject_mask = prepared
@@ -270,6 +299,15 @@ class Solver:
         if self.feature_model is not None:
             features = self.feature_model(features)                   # bm/solver.py:304-320
         return estimate, features, features_mask, reject_mask
+
+    def _loss_mask(self, features_mask):
+        """The mask a regression loss gets: None (all true) unless ``mask_loss`` (bm/solver.py:251-253)."""
+        if not self.mask_loss:
+            return None
+        if not self.check_finite:
+            # no flag word to defer to: the reference's assert, synchronising (bm/solver.py:354-356)
+            assert bool(features_mask.any()), "no mask!"
+        return features_mask if features_mask.is_contiguous() else features_mask.contiguous()
 
     def _all_models(self):
         return [self.model] + ([self.feature_model] if self.feature_model is not None else [])
@@ -332,10 +370,15 @@ class Solver:
                                                                      defer_flags=True)
         elif not self._substituted:
             self._last_batch = batch
-        output, target_offset, valid = self._candidates(output)
-        output = self._complete_with_pool(output, training=True)
-        loss = self.loss(estimate, output, features_mask, target_offset=target_offset, candidate_valid=valid,
-                         **self._gathered_estimates(estimate))
+        if self.regression:
+            loss = self.loss(estimate, output, self._loss_mask(features_mask))
+            # the flag word now holds this batch's finiteness verdict AND the loss' "no mask!" bit
+            self._flag_ticket = self._post_flags()
+        else:
+            output, target_offset, valid = self._candidates(output)
+            output = self._complete_with_pool(output, training=True)
+            loss = self.loss(estimate, output, features_mask, target_offset=target_offset, candidate_valid=valid,
+                             **self._gathered_estimates(estimate))
         if next_batch is not None:
             self.prefetch(next_batch)       # the next step's candidate all-gather runs next to this backward
         # bm/solver.py:375-380: `training_penalty` of every module that has one (ChannelMerger with merger_penalty:
@@ -429,10 +472,13 @@ class Solver:
             m.train(False)
         self.loss.train(False)
         estimate, output, features_mask, _ = self._process_batch(batch, training=False)
-        output, target_offset, valid = self._candidates(output)
-        output = self._complete_with_pool(output, training=False)
-        loss = self.loss(estimate, output, features_mask, target_offset=target_offset, candidate_valid=valid,
-                         **self._gathered_estimates(estimate))
+        if self.regression:
+            loss = self.loss(estimate, output, self._loss_mask(features_mask))
+        else:
+            output, target_offset, valid = self._candidates(output)
+            output = self._complete_with_pool(output, training=False)
+            loss = self.loss(estimate, output, features_mask, target_offset=target_offset, candidate_valid=valid,
+                             **self._gathered_estimates(estimate))
         # the mask assert of THIS call is deferred to the flag word: an evaluation loop has no next train_step that
         # would read it (one small read-back per evaluation batch; the reference's assert synchronises as well)
         self.check_pending_flags()

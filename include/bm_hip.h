@@ -248,6 +248,34 @@ int bm_clip_ce_masked(const float* part, int nsplit, const float* inv_norm, cons
 int bm_clip_ce_cols(const float* scores, const float* inv_norm, float* dscaled, float* loss_col, float* loss, int B,
                     int Bc, int target_offset, float w_row, float w_col, void* stream);
 
+/* ---- regression objective: L1Loss / L2Loss and their test metrics (regress.hip)  bm/losses.py:11-26 ----
+ * est, out: fp32 [B][F][T]; mask: null (all true), mask_mode 1 = bytes [B][1][T] broadcast over F (SegmentBatch
+ * .features_mask), mask_mode 2 = bytes [B][F][T]; nonzero = selected.  kind 0 = L1 (|d|), 1 = MSE (d^2), d = e - o.
+ * Forward (ONE launch): *loss = sum_selected w(d) / count (fp64 partials, folded in a fixed order by the workgroup that
+ * finishes last), *count = number of selected elements -- torch.nn.L1Loss() / MSELoss() on est[mask.expand_as(est)].
+ * count == 0 gives NaN and raises bit 2 of flag (nullable; the Solver's flag word slot 2): the reference's "no mask!"
+ * assert, bm/solver.py:354-356.  `workspace` (bm_regress_workspace_bytes) holds the partials and the ticket counters:
+ * ZEROED by the caller once; every launch leaves its counter at zero again. */
+long bm_regress_workspace_bytes(void);
+int bm_regress_loss_fwd(const float* est, const float* out, const unsigned char* mask, int mask_mode, int B, int F,
+                        int T, int kind, float* loss, double* count, void* workspace, long workspace_bytes, int* flag,
+                        void* stream);
+/* Backward (ONE launch): d_est = g * w'(d) * m / count with g = *grad_out and count read on the device (w' = sign,
+ * sign(0) = 0, for L1; 2 d for MSE); d_out (nullable: a learnable feature model) = -d_est.  amax_out (nullable amax
+ * slot, compute mode f16x2) receives max |d_est| and amax_rows_out ([F] floats, nullable) the per-channel maxima, like
+ * bm_glu_bwd / bm_act_bn_bwd publish them: the head's backward contractions need no bm_amax pass. */
+int bm_regress_loss_bwd(const float* est, const float* out, const unsigned char* mask, int mask_mode, int B, int F,
+                        int T, int kind, const float* grad_out, const double* count, float* d_est, float* d_out,
+                        float* amax_out, float* amax_rows_out, void* workspace, long workspace_bytes, void* stream);
+/* Test metrics, bm/metrics.py:37-170 with dim = 0 (OnlineCorrelation, L1Reg, L2Reg; bm/play.py:149-151 casts to
+ * double): acc = 8 planes of [F][T - t0] fp64 accumulators, += per (f, t) over b, in b order: sum l r m, sum l m,
+ * sum r m, sum (l m)^2, sum (r m)^2, sum m, sum ((l - r) m)^2, sum |(l - r) m|.  Only the columns t >= t0 (trim_offset,
+ * bm/play.py:144-147).  Rows T floats apart, segments est_bstride / out_bstride floats and mask_bstride bytes apart;
+ * mask_full = 0: mask [B][1][T], 1: [B][F][T]; mask null = all true. */
+int bm_regress_metric_update(const float* est, long est_bstride, const float* out, long out_bstride,
+                             const unsigned char* mask, long mask_bstride, int mask_full, int B, int F, int T, int t0,
+                             double* acc, void* stream);
+
 /* Gradient of ClipLoss w.r.t. the candidates (learnable feature model, bm/solver.py:304-320):
  * coef[o] = alpha * (sum_b dscaled[b,o]*scores[b,o]) / |cand_o| ;  y[r] -= coef[r] * x[r]. */
 int bm_clip_cand_coef(const float* dscaled, const float* scores, const float* inv_norm,
