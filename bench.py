@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark of the MI355X-native SimpleConv + ClipLoss training step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: set-up, W warm-up steps, K timed steps, the
+optional dump, the result line.  ``--full`` adds every side measurement listed below, after the timed steps.
 
 With N > 1 and no torchrun environment the script re-launches itself as
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py``
@@ -17,7 +20,8 @@ timed region.  With N > 1 every rank processes its own 256 segments (weak scalin
 all-gathered so the negatives pool is whole-node (configs[3]) and gradients go through ONE in-place
 reduce-scatter + all-gather on the flat bucket, on RCCL behind the C-ABI (bm_comm_*).
 
-Rank 0 prints ONE JSON line with the driver's contract plus
+Rank 0 prints ONE JSON line with the driver's contract (``metric``, ``value``, ``unit``, ``higher_is_better``,
+``dtype``, ``ms_per_step``, ...) and the configuration; with ``--full`` (each ``--no-*`` option drops a part) also
   ``roofline``       dominant kernel, timed with HIP events on the launch stream in a second, untimed
                      pass over the same batches right after the timed region (no event records inside
                      the timed region); ``traffic`` = HBM bytes per launch MEASURED IN THIS RUN by two
@@ -30,7 +34,9 @@ Rank 0 prints ONE JSON line with the driver's contract plus
                      reference modules themselves need /root/reference, absent on the GPU box; timed beside
                      the live reference in the build container: profiles/r5_port_vs_reference.json) on the
                      configuration of ``value`` itself (cfg2, batch 256, 32 threads), with cfg1 (batch 16,
-                     1 thread = what bm/train.py:182 configures, and 32 threads) as a sub-block.
+                     1 thread = what bm/train.py:182 configures, and 32 threads) as a sub-block;
+  ``sustained``, ``pcie_inclusive``, ``other_fp32_modes``, ``dvfs_probe``, ``roofline_retrieval``, ``retrieval``,
+  ``retrieval_parity``   the side blocks of main(), each described where it runs.
 
 ``--dump-outputs DIR`` writes what the last timed step left to its caller -- the loss and the model's state_dict --
 as ``DIR/<name>.npy`` (rank 0, float32 / float64, a seeded sample of the large arrays beyond 48 MB in all): the inputs
@@ -132,9 +138,9 @@ def _pmc_counter_csv(counter, args, timeout):
         return None
     tmp = tempfile.mkdtemp(prefix="bm_pmc_", dir="/tmp")
     cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "bench", "--",
-           sys.executable, str(Path(__file__).resolve()), "--steps", "2", "--warmup", "1", "--workload", args.workload,
-           "--batch", str(args.batch), "--dtype", args.dtype, "--no-cpu-baseline", "--accuracy-steps", "0", "--no-exact",
-           "--no-clip", "--no-side-blocks", "--no-pmc"]
+           sys.executable, str(Path(__file__).resolve()), "--full", "--steps", "2", "--warmup", "1",
+           "--workload", args.workload, "--batch", str(args.batch), "--dtype", args.dtype, "--no-cpu-baseline",
+           "--accuracy-steps", "0", "--no-exact", "--no-clip", "--no-side-blocks", "--no-pmc"]
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "BM_FORCE_DISTRIBUTED"):
         env.pop(k, None)
@@ -205,8 +211,8 @@ def live_pmc_traffic(kernel_label, args, child_steps=5, timeout=90):
     return {"hbm_bytes_per_launch": per_launch, "launches_counted": launches, "step_hbm_bytes": step_bytes,
             "child_steps": child_steps, "seconds": time.perf_counter() - t0, "per_kernel": top,
             "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over a child "
-                   "`bench.py --steps 2 --warmup 1` of the same workload (1 warm-up + 2 timed + 2 event-pass steps = "
-                   "5 steps; the child's set-up launches are counted into step_hbm_bytes: < 1 %); "
+                   "`bench.py --full --steps 2 --warmup 1` of the same workload (1 warm-up + 2 timed + 2 event-pass "
+                   "steps = 5 steps; the child's set-up launches are counted into step_hbm_bytes: < 1 %); "
                    "bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per MI355X_MICROARCH.md"}
 
 
@@ -680,6 +686,11 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg5"])
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--negatives", default=None, choices=["local", "node"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements (HIP-event pass with roofline and "
+                         "comm_ms, sustained / pcie-inclusive / other fp32 modes / DVFS probe, ClipLoss and retrieval "
+                         "rooflines, retrieval accuracy and parity, live PMC traffic, CPU baseline); the --no-* "
+                         "options and --accuracy-steps / --sustained-steps shape this part and do nothing without it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--accuracy-steps", type=int, default=60,
                     help="second half of the metric: after the timed region (never part of `value`), train a fresh "
@@ -763,6 +774,41 @@ def main():
         # a throughput number of a diverged run is worthless (and flattering: the matrix pipe clocks higher on NaNs)
         raise SystemExit(f"bench: the training loss is not finite after the timed region ({final_loss})")
 
+    seg_flops = algorithmic_flops_per_segment(c["C"], c["T"], c["F"])
+    out = {
+        "metric": ("segments/s, 208-ch x 360-sample SimpleConv + ClipLoss training step" if not zero_operands else
+                   "DVFS PROBE ON ALL-ZERO OPERANDS -- not a result"),
+        "value": world * B * args.steps / elapsed,
+        "unit": "segments/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": MODE_DTYPE[args.dtype],
+        "compute_mode": args.dtype, "data": "synthetic",
+        "config": {"workload": f"{args.workload}: gwilliams2022-shaped MEG C={c['C']} T={c['T']}, "
+                               f"F={c['F']} features, {c['S']} subjects, clip_conv SimpleConv "
+                               f"({n_params} params) + ClipLoss + Adam",
+                   "batch_per_gpu": B, "global_batch": world * B, "negatives": negatives,
+                   "parallelism": f"dp{world}", "comm": distrib.comm_kind(), "rccl_world": distrib.reported_world(),
+                   "candidate_gather": ("prefetched one step ahead on a side stream" if prefetch else
+                                        ("in front of the forward" if negatives == "node" else "none")),
+                   "distinct_batches": stream.n, "final_loss": final_loss,
+                   "step_tflops": seg_flops * B * world * args.steps / elapsed / 1e12},
+        "full": args.full,
+    }
+    out["dump_outputs"] = dumped
+    out["comm_world_reported"] = distrib.reported_world()
+    # one-pass BatchNorm backward: workgroups that gave up polling for a partner's sums and computed them themselves
+    # (slow path, never wrong) since the process started -- 0 unless partners were not co-resident
+    out["bn_bwd_fused_fallback_workgroups"] = int(_lib.lib().bm_act_bn_bwd_fused_fallbacks())
+    if not args.full:
+        distrib.barrier()
+        if rank == 0:
+            flush_c_stdio()
+            print(json.dumps(out), flush=True)
+        return
+
+    # --full from here on: side measurements after the headline figure, none of them part of `value`.
     # second pass over the same stream with per-launch HIP events (NOT part of `value`)
     timer = hip_ops.KernelTimer()
     hip_ops.set_kernel_timer(timer)
@@ -835,7 +881,6 @@ def main():
     dom = max(ksum, key=lambda k: ksum[k]["avg_ms"] * ksum[k]["launches"])
     d = ksum[dom]
     achieved = d["flops_per_launch"] / (d["avg_ms"] * 1e-3) / 1e12
-    seg_flops = algorithmic_flops_per_segment(c["C"], c["T"], c["F"])
     traffic, traffic_src, traffic_avg_ms = pmc_traffic(dom)
     # HBM traffic measured in THIS run (rocprofv3 children while this process leaves the GPU alone); they overlap with the
     # CPU baseline, which keeps the GPU idle anyway.  Collected further down; the committed summary is the fallback.
@@ -852,56 +897,33 @@ def main():
     peak_tf = MODE_PEAK_TFLOPS[args.dtype]
     total_kernel_ms = sum(v["avg_ms"] * v["launches"] for v in ksum.values()) / args.steps
     step_bytes = algorithmic_bytes_per_step(c["C"], c["T"], c["F"], B, n_params)
-    out = {
-        "metric": ("segments/s, 208-ch x 360-sample SimpleConv + ClipLoss training step" if not zero_operands else
-                   "DVFS PROBE ON ALL-ZERO OPERANDS -- not a result"),
-        "value": world * B * args.steps / elapsed,
-        "unit": "segments/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": MODE_DTYPE[args.dtype],
-        "compute_mode": args.dtype, "data": "synthetic",
-        "config": {"workload": f"{args.workload}: gwilliams2022-shaped MEG C={c['C']} T={c['T']}, "
-                               f"F={c['F']} features, {c['S']} subjects, clip_conv SimpleConv "
-                               f"({n_params} params) + ClipLoss + Adam",
-                   "batch_per_gpu": B, "global_batch": world * B, "negatives": negatives,
-                   "parallelism": f"dp{world}", "comm": distrib.comm_kind(), "rccl_world": distrib.reported_world(),
-                   "candidate_gather": ("prefetched one step ahead on a side stream" if prefetch else
-                                        ("in front of the forward" if negatives == "node" else "none")),
-                   "distinct_batches": stream.n, "final_loss": final_loss,
-                   "step_tflops": seg_flops * B * world * args.steps / elapsed / 1e12},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved,
-                     "peak": peak_tf, "unit": "TFLOP/s", "frac": achieved / peak_tf,
-                     # information: the same ratio against what a register-only MFMA loop on random 16-bit operands
-                     # sustains on this chip (1 790 TF at a power-throttled ~1.75 GHz, scripts/micro/mfma_peak.hip)
-                     "frac_of_sustained_mfma": (achieved / (peak_tf * 1790.0 / 2500.0)
-                                                if args.dtype in ("f16x2", "f32x3") else None),
-                     "traffic": traffic,
-                     "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, separate passes)",
-                     "traffic_source": "committed:" + str(traffic_src), "traffic_stale": traffic_stale,
-                     "traffic_summary_avg_launch_ms": traffic_avg_ms,
+    out["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": achieved,
+                       "peak": peak_tf, "unit": "TFLOP/s", "frac": achieved / peak_tf,
+                       # information: the same ratio against what a register-only MFMA loop on random 16-bit operands
+                       # sustains on this chip (1 790 TF at a power-throttled ~1.75 GHz, scripts/micro/mfma_peak.hip)
+                       "frac_of_sustained_mfma": (achieved / (peak_tf * 1790.0 / 2500.0)
+                                                  if args.dtype in ("f16x2", "f32x3") else None),
+                       "traffic": traffic,
+                       "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, separate passes)",
+                       "traffic_source": "committed:" + str(traffic_src), "traffic_stale": traffic_stale,
+                       "traffic_summary_avg_launch_ms": traffic_avg_ms,
 
-                     "avg_launch_ms": d["avg_ms"], "launches_per_step": d["launches"] / args.steps,
-                     "median_launch_ms": d["median_ms"],
-                     "event_outliers_dropped": {k: v["outliers"] for k, v in ksum.items() if v["outliers"]},
-                     "algorithmic_flops_per_launch": d["flops_per_launch"],
-                     "mfma_kernels_ms_per_step": total_kernel_ms,
-                     "event_pass_ms_per_step": event_pass_elapsed / args.steps * 1e3,
-                     "per_kernel_ms_per_step": {k: v["avg_ms"] * v["launches"] / args.steps for k, v in
-                                                sorted(ksum.items(), key=lambda kv: -kv[1]["avg_ms"] * kv[1]["launches"])},
-                     "hbm_roofline_frac_step": step_bytes / (PEAK_HBM_GBS * 1e9) / (elapsed / args.steps),
-                     "algorithmic_bytes_per_step": step_bytes},
-    }
+                       "avg_launch_ms": d["avg_ms"], "launches_per_step": d["launches"] / args.steps,
+                       "median_launch_ms": d["median_ms"],
+                       "event_outliers_dropped": {k: v["outliers"] for k, v in ksum.items() if v["outliers"]},
+                       "algorithmic_flops_per_launch": d["flops_per_launch"],
+                       "mfma_kernels_ms_per_step": total_kernel_ms,
+                       "event_pass_ms_per_step": event_pass_elapsed / args.steps * 1e3,
+                       "per_kernel_ms_per_step": {
+                           k: v["avg_ms"] * v["launches"] / args.steps for k, v in
+                           sorted(ksum.items(), key=lambda kv: -kv[1]["avg_ms"] * kv[1]["launches"])},
+                       "hbm_roofline_frac_step": step_bytes / (PEAK_HBM_GBS * 1e9) / (elapsed / args.steps),
+                       "algorithmic_bytes_per_step": step_bytes}
     # per-phase communication times of the event pass (HIP events on the stream each collective is enqueued on): what a
     # first real multi-GPU run needs to explain itself.  `cand_gather` runs on the side stream under the backward pass;
     # `gather_wait` is the part of it the compute stream actually waits for.
     out["comm_ms"] = comm_ms
-    out["dump_outputs"] = dumped
-    out["comm_world_reported"] = distrib.reported_world()
-    # one-pass BatchNorm backward: workgroups that gave up polling for a partner's sums and computed them themselves
-    # (slow path, never wrong) since the process started -- 0 unless partners were not co-resident
-    out["bn_bwd_fused_fallback_workgroups"] = int(_lib.lib().bm_act_bn_bwd_fused_fallbacks())
+    out["bn_bwd_fused_fallback_workgroups"] = int(_lib.lib().bm_act_bn_bwd_fused_fallbacks())     # side blocks included
     out["dvfs_probe"] = dvfs
     out["sustained"] = sustained
     out["pcie_inclusive"] = pcie

@@ -7,7 +7,7 @@ cd $R; mkdir -p gpurun_out
 TAG=${1:-final}
 bash scripts/gpu_check.sh $TAG 1500 prof 2>&1 | tail -30
 cp gpurun_out/${TAG}_pmc_summary.json gpurun_out/${TAG}_pmc_summary_onbox.json 2>/dev/null
-SIDE="--no-cpu-baseline --accuracy-steps 0 --no-exact --no-clip --no-side-blocks"
+SIDE="--full --no-cpu-baseline --accuracy-steps 0 --no-exact --no-clip --no-side-blocks"
 timeout 300 python bench.py --workload cfg3 $SIDE > gpurun_out/${TAG}_bench_cfg3.json 2>/dev/null; echo "cfg3 rc=$?"
 timeout 300 python bench.py --workload cfg5 $SIDE > gpurun_out/${TAG}_bench_cfg5.json 2>/dev/null; echo "cfg5 rc=$?"
 # power / clock trace next to a 400-step run (rocm-smi sampled every 100 ms; read-only)

@@ -936,6 +936,32 @@ def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
     assert heads.dtype == np.float32 and np.isfinite(heads).all()
 
 
+def test_bench_plain_run_prints_the_headline_only():
+    """A plain `bench.py` run (no `--full`) sets up, warms up, times its steps and prints the result line with the
+    driver's contract and the configuration; the side measurements are left to `--full`."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "BM_FORCE_DISTRIBUTED"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                         env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, lines[:5]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 2 and line["warmup"] == 1
+    assert line["unit"] == "segments/s" and line["higher_is_better"] is True and line["dtype"].startswith("f32")
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] - 256e3) < 1e-6 * 256e3
+    for k in ("roofline", "comm_ms", "sustained", "pcie_inclusive", "dvfs_probe", "other_fp32_modes", "roofline_clip",
+              "roofline_retrieval", "retrieval", "retrieval_parity", "cpu_baseline"):
+        assert k not in line, k
+
+
 # Dimensions of the long-horizon parity runs (this test and bench.py's `retrieval_parity`): every contraction of the
 # step runs in the SAME kernels as the headline benchmark -- the wide f16x2 conv (T > 128, M >= 96), the wide f16x2
 # weight gradients (M a multiple of 256 / 320 within 25 %, Cn of 64) and the f16x2 score contraction (batch >= 128);
