@@ -24,6 +24,8 @@ int bm_check_launch(const char* what);
     } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// Picks the tile (128 or 64 rows / cols) with the least padding.
+static inline bool prefer_big(int n) { return (long)cdiv(n, 128) * 128 <= (long)cdiv(n, 64) * 64; }
 
 // n / d for 32-bit n by multiply-high (Granlund & Montgomery): the flat-index kernels split an element index into
 // (row, column) once per vector; a 64-bit hardware-less division there cost more instructions than the erf.

@@ -1,13 +1,12 @@
 // Shared by the two wide f16x2 conv translation units (conv_nn_h2w.hip: the production main loop, conv_nn_h2d.hip: the
-// round-2..5 main loop kept for A/B runs): argument block, scale rule, operand split, tile epilogue.
+// round-2..5 main loop kept for A/B runs): argument block, operand split, tile epilogue (the scale rule: mfma_split.h).
 #pragma once
 #include <cstdlib>
 #include <cstring>
-#include <utility>
 #include "conv_common.h"
+#include "mfma_split.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4h __attribute__((ext_vector_type(4)));
 
 #define HBN 192           // columns of the workgroup tile (2 wavefront columns x 3 blocks)
@@ -21,22 +20,6 @@ struct ConvH2Args {
     BmAmaxDst y_amax;         // where max |y_out| goes (bm_publish_amax): per-workgroup partials
 };
 
-// Power-of-two scale s with amax * s in [2^14, 2^15), and its exact inverse.  amax == 0 / subnormal / inf /
-// nan: s = 1 (non-finite operands then propagate through the split as inf / nan like in fp32).
-__host__ __device__ __forceinline__ void h2_scale_from_amax(float amax, float& s, float& inv) {
-    unsigned bits;
-    memcpy(&bits, &amax, 4);
-    const unsigned e = (bits >> 23) & 0xffu;
-    int se = 127;
-    if (e != 0u && e != 255u) {
-        se = 268 - (int)e;              // 127 + 14 - (e - 127)
-        se = se > 253 ? 253 : (se < 1 ? 1 : se);
-    }
-    const unsigned sb = (unsigned)se << 23, ib = (unsigned)(254 - se) << 23;
-    memcpy(&s, &sb, 4);
-    memcpy(&inv, &ib, 4);
-}
-
 // 8 fp32 values (already scaled) -> f16 planes hi, lo
 __device__ __forceinline__ void split8h(const float* f, float s, u32x4& hi, u32x4& lo) {
     f16x8 h, l;
@@ -49,26 +32,6 @@ __device__ __forceinline__ void split8h(const float* f, float s, u32x4& hi, u32x
     }
     hi = __builtin_bit_cast(u32x4, h);
     lo = __builtin_bit_cast(u32x4, l);
-}
-
-// two fp32 values -> scaled f16 pairs: hi = f16(x * s), lo = f16(x * s - hi) (the product is exact, s is a power
-// of two; the difference is exact in fp32), written straight into the halves of the packed results: 4 VALU
-__device__ __forceinline__ void ch_split_pair(float x0, float x1, float s, unsigned& hi, unsigned& lo) {
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(hi), "=&v"(lo)
-        : "v"(x0), "v"(x1), "v"(s));
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void h2_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void h2_static_for(F&& f) {
-    h2_static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 __device__ __forceinline__ float ch_ld32(i32x4h rs, int voff) {
@@ -143,7 +106,7 @@ __device__ __forceinline__ void h2_residual_add(const H2Plain& e, f32x16 (&acc)[
     constexpr int NBLK = MW * 3, D = 3;
     float rv[D][16];
     const bool cok[3] = {col0 < T, col0 + 32 < T, col0 + 64 < T};
-    h2_static_for<NBLK + D>([&](auto ic) __attribute__((always_inline)) {
+    bm_static_for<NBLK + D>([&](auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i >= D) {                                   // block i - D has landed
             constexpr int b = i - D, nt = b / MW, mt = b % MW;
@@ -218,7 +181,7 @@ __device__ __forceinline__ void h2_tile_stats(const ConvNNArgs& a, f32x16 (&acc)
     // wave-uniform: every column of the wavefront's 96 lies inside T (3 of the 4 wavefront tiles of a T = 360 segment)
     const bool all_in = __builtin_amdgcn_readfirstlane(col0 - (lane & 31)) + 95 < a.T;
     const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
-    h2_static_for<MW>([&](auto mc) __attribute__((always_inline)) {
+    bm_static_for<MW>([&](auto mc) __attribute__((always_inline)) {
         constexpr int mt = decltype(mc)::value;
         float s1[16], s2[16];
         if (all_in) {

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
     // packed weights in 16-byte slots: [g][chunk32][tap][plane][4][Mpad]
     const u32x4* wg = reinterpret_cast<const u32x4*>(a.wp) + (long)g * nchunk32 * KS * 8 * a.Mpad + m0 + lane;
     float sx, sx_inv;
-    h2_scale_from_amax(bm_amax_load(args.x_amax), sx, sx_inv);
+    bm_scale_from_amax(bm_amax_load(args.x_amax), sx, sx_inv);
 
     // input window of this segment through a bounds-checked buffer descriptor: channels past Cin read 0
     const unsigned long long xaddr = (unsigned long long)(a.x + (long)b * a.x_bstride);
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
 #endif
     for (int c16 = 0; c16 < n16; ++c16) {
         const int xbuf = c16 & 1;
-        h2_static_for<KS>([&](auto jc) __attribute__((always_inline)) {
+        bm_static_for<KS>([&](auto jc) __attribute__((always_inline)) {
             constexpr int j = decltype(jc)::value;
             CH_T(0)
             const int ab_next = ab3 == 2 ? 0 : ab3 + 1;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
             const u32x4* dsrc = wg + ((long)((dc16 >> 1) * KS + djj) * 8 + (dc16 & 1) * 2) * a.Mpad;
             const int cb = (c16 + (KS == 1 ? 2 : 1)) * 16 * crow + xoff0;
             u32x4* xd = Xs + (xbuf ^ 1) * HXSLAB + tid;
-            h2_static_for<3 * TN>([&](auto nc) __attribute__((always_inline)) {
+            bm_static_for<3 * TN>([&](auto nc) __attribute__((always_inline)) {
                 constexpr int n = decltype(nc)::value;
                 constexpr int term = n / TN, w = n % TN, mt = w / NW, nt = w % NW;
                 constexpr int pa = term == 1 ? 1 : 0, pb = term == 0 ? 1 : 0;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
                     constexpr int q = n - WS0;
                     if constexpr (KS != 1 && j == 0) {                     // window loads, 16 over WSN slots
                         constexpr int r0 = (q * 16 + WSN - 1) / WSN, r1 = ((q + 1) * 16 + WSN - 1) / WSN;
-                        h2_static_for<r1 - r0>([&](auto rc) __attribute__((always_inline)) {
+                        bm_static_for<r1 - r0>([&](auto rc) __attribute__((always_inline)) {
                             constexpr int r = r0 + decltype(rc)::value;
                             if constexpr (r < 16) xreg[r] = ch_ld32(xr, cb + r * crow);
                         });
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
                             if (KS == 1) CH_WAIT_X(MW) else CH_WAIT_X(2 * MW)
                         }
                         constexpr int u0 = (q * 8 + WSN - 1) / WSN, u1 = ((q + 1) * 8 + WSN - 1) / WSN;
-                        h2_static_for<u1 - u0>([&](auto uc) __attribute__((always_inline)) {
+                        bm_static_for<u1 - u0>([&](auto uc) __attribute__((always_inline)) {
                             constexpr int u = u0 + decltype(uc)::value;
                             if constexpr (u < 8) {
                                 // the group of pairs 0-3 is written one unit late: not in front of term 2's wait
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2d_kernel(ConvH2Args args) {
                                     xd[(0 * 2 + 0) * HXWP] = u32x4{ph[0], ph[1], ph[2], ph[3]};
                                     xd[(1 * 2 + 0) * HXWP] = u32x4{pw[0], pw[1], pw[2], pw[3]};
                                 }
-                                ch_split_pair(xreg[2 * u], xreg[2 * u + 1], sx, ph[u & 3], pw[u & 3]);
+                                bm_split_pair(xreg[2 * u], xreg[2 * u + 1], sx, ph[u & 3], pw[u & 3]);
                                 if constexpr (u == 7) {
                                     xd[(0 * 2 + 1) * HXWP] = u32x4{ph[0], ph[1], ph[2], ph[3]};
                                     xd[(1 * 2 + 1) * HXWP] = u32x4{pw[0], pw[1], pw[2], pw[3]};

@@ -51,14 +51,7 @@ extern "C" int bm_debug_trace_read_conv(unsigned* out) {
 }
 #endif
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t h2_rsrc(const void* p, unsigned bytes) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-// the two halves of ch_split_pair as separate statements (2 VALU each): they sit in different MFMA slots
+// the two halves of the one-scale bm_split_pair as separate statements (2 VALU each): they sit in different MFMA slots
 __device__ __forceinline__ void ch_split_hi(float x0, float x1, float s, unsigned& hi) {
     asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
         "v_fma_mixhi_f16 %0, %2, %3, 0" : "=&v"(hi) : "v"(x0), "v"(x1), "v"(s));
@@ -144,18 +137,18 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
     const int g = a.widx ? a.widx[b] : 0;
     const int n16 = 2 * a.nchunk;                     // 16-channel chunks, an even number; channels past Cin read 0
     float sx, sx_inv;
-    h2_scale_from_amax(bm_amax_load(args.x_amax), sx, sx_inv);
+    bm_scale_from_amax(bm_amax_load(args.x_amax), sx, sx_inv);
 
     // this group's packed planes [chunk32][tap][plane][4][Mpad] x 16 B behind one descriptor; a lane's slot inside a
     // (stage, plane): (h Mpad + row) x 16, row block mt = an immediate (512 mt), stage and plane = the scalar offset
     const long gslots = (long)a.nchunk * KS * 8 * a.Mpad;
-    const __amdgpu_buffer_rsrc_t wr = h2_rsrc(reinterpret_cast<const u32x4*>(a.wp) + (long)g * gslots, (unsigned)(gslots * 16));
+    const __amdgpu_buffer_rsrc_t wr = bm_buffer_rsrc(reinterpret_cast<const u32x4*>(a.wp) + (long)g * gslots, (unsigned)(gslots * 16));
     const int wvoff = (h * a.Mpad + m0 + wm * (MW * 32) + nl) * 16;
     const int pstride = 4 * a.Mpad * 16;              // bytes between the two planes of a stage
     // input window of this segment through a bounds-checked descriptor: channels past Cin read 0; thread `tid`
     // stages window column tid (both 8-channel groups); columns outside [0, T) or past the window get an offset
     // that stays out of range for every channel -> they read as 0 (conv zero padding)
-    const __amdgpu_buffer_rsrc_t xr = h2_rsrc(a.x + (long)b * a.x_bstride, (unsigned)(a.Cin * a.T * 4));
+    const __amdgpu_buffer_rsrc_t xr = bm_buffer_rsrc(a.x + (long)b * a.x_bstride, (unsigned)(a.Cin * a.T * 4));
     const int tcol = n0 - halo + tid;
     const int xoff0 = (tid < XW && tcol >= 0 && tcol < a.T) ? tcol * 4 : 0x40000000;
     const int crow = a.T * 4;
@@ -185,9 +178,9 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
 
     // prologue: the window of chunk 0 (requested first: it comes from HBM), A of stage 0; split + written to X
     // buffer 0; 1x1: the window of chunk 1 requested behind it; barrier; B of stage 0
-    h2_static_for<16>([&](auto rc) __attribute__((always_inline)) { H2R_LOAD_X(decltype(rc)::value, xoff0) });
-    h2_static_for<NA>([&](auto kc) __attribute__((always_inline)) { H2R_LOAD_A(0, decltype(kc)::value, 0) });
-    h2_static_for<8>([&](auto uc) __attribute__((always_inline)) {
+    bm_static_for<16>([&](auto rc) __attribute__((always_inline)) { H2R_LOAD_X(decltype(rc)::value, xoff0) });
+    bm_static_for<NA>([&](auto kc) __attribute__((always_inline)) { H2R_LOAD_A(0, decltype(kc)::value, 0) });
+    bm_static_for<8>([&](auto uc) __attribute__((always_inline)) {
         constexpr int u = decltype(uc)::value;
         ch_split_hi(xreg[2 * u], xreg[2 * u + 1], sx, ph[u]);
         ch_split_lo(xreg[2 * u], xreg[2 * u + 1], sx, ph[u], pw[u]);
@@ -196,9 +189,9 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
     xwr[(1 * 2 + 0) * HXWP] = u32x4{pw[0], pw[1], pw[2], pw[3]};
     xwr[(0 * 2 + 1) * HXWP] = u32x4{ph[4], ph[5], ph[6], ph[7]};
     xwr[(1 * 2 + 1) * HXWP] = u32x4{pw[4], pw[5], pw[6], pw[7]};
-    if (KS == 1) h2_static_for<16>([&](auto rc) __attribute__((always_inline)) { H2R_LOAD_X(decltype(rc)::value, 16 * crow + xoff0) });
+    if (KS == 1) bm_static_for<16>([&](auto rc) __attribute__((always_inline)) { H2R_LOAD_X(decltype(rc)::value, 16 * crow + xoff0) });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    h2_static_for<NB>([&](auto ic) __attribute__((always_inline)) {
+    bm_static_for<NB>([&](auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
         bf[0][i / NW][i % NW] = __builtin_bit_cast(f16x8, xrd[(i / NW) * 2 * HXWP + (i % NW) * 32]);
     });
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
         // the window this stage requests (3 taps: chunk c16 + 1, in tap 0; 1x1: chunk c16 + 2) / splits (chunk c16 + 1)
         const int cb = (c16 + (KS == 1 ? 2 : 1)) * 16 * crow + xoff0;
         u32x4* xw = xwr + ((c16 + 1) & 1) * HXSLAB;
-        h2_static_for<NS>([&](auto nc) __attribute__((always_inline)) {
+        bm_static_for<NS>([&](auto nc) __attribute__((always_inline)) {
             constexpr int n = decltype(nc)::value;
             constexpr int term = n / TN, w = n % TN, mt = w / NW, nt = w % NW;
             constexpr int pa = term == 0 ? 1 : 0, pb = term == 1 ? 1 : 0;
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
                 constexpr int f = (n / 4) * 3 + n % 4 - 1;
                 constexpr int L = h2r_nitems<KS, j, NB>();
                 constexpr int i0 = (f * L + NF - 1) / NF, i1 = ((f + 1) * L + NF - 1) / NF;
-                h2_static_for<i1 - i0>([&](auto ic) __attribute__((always_inline)) {
+                bm_static_for<i1 - i0>([&](auto ic) __attribute__((always_inline)) {
                     constexpr H2RItem it = h2r_item<KS, j, NB>(i0 + decltype(ic)::value);
                     if constexpr (it.kind == H2R_WLOAD) {
                         H2R_LOAD_X(it.arg, cb)
@@ -265,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void conv_nn_h2w_kernel(ConvH2Args args) {
     // a chunk whose first stage runs on register set CP (3 taps: the sets alternate inside the chunk)
     auto chunk = [&](int c16, auto cpc) __attribute__((always_inline)) {
         constexpr int cp = decltype(cpc)::value;
-        h2_static_for<KS>([&](auto jc) __attribute__((always_inline)) {
+        bm_static_for<KS>([&](auto jc) __attribute__((always_inline)) {
             constexpr int j = decltype(jc)::value;
             stage(c16, jc, std::integral_constant<int, (cp + j) & 1>{});
         });
@@ -400,7 +393,7 @@ __device__ __forceinline__ void pack_h2_rows(const PackH2Job& jb, int block, flo
         for (int i = lane; i < nk; i += 64) mx = fmaxf(mx, fabsf(tile[wave * nk + i]));
         mx = bm_wave_max(mx);
         float s, inv;
-        h2_scale_from_amax(mx, s, inv);
+        bm_scale_from_amax(mx, s, inv);
         if (lane == 0) {
             rs[wave] = s;
             jb.wscale[(long)g * Mpad + m0 + wave] = inv;

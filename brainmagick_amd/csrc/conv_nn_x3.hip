@@ -18,31 +18,10 @@
 // registers while the MFMAs run.
 #include <cstdlib>
 #include "conv_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_split.h"
 
 #define XC 32             // channels per chunk
 #define XG (XC / 8)       // 8-channel groups per chunk
-
-template <int N> struct FVecX { typedef float type __attribute__((ext_vector_type(N))); };
-template <int N> struct UVecX { typedef unsigned int type __attribute__((ext_vector_type(N))); };
-
-// exact 3-way split of 8 fp32 values into bf16 planes (hi, mid, lo)
-__device__ __forceinline__ void split8(const float* f, u32x4& hi, u32x4& mid, u32x4& lo) {
-    bf16x8 h, m, l;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a = (__bf16)f[i];
-        const float r1 = f[i] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        const float r2 = r1 - (float)b;
-        h[i] = a; m[i] = b; l[i] = (__bf16)r2;
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    mid = __builtin_bit_cast(u32x4, m);
-    lo = __builtin_bit_cast(u32x4, l);
-}
 
 template <int MT, int KS>
 __global__ __launch_bounds__(256, 2) void conv_nn_x3_kernel(ConvNNArgs a) {
@@ -82,8 +61,8 @@ __global__ __launch_bounds__(256, 2) void conv_nn_x3_kernel(ConvNNArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
 
-    typename UVecX<4 * AIT>::type areg;
-    typename FVecX<8 * NIT>::type xreg;
+    typename UVec<4 * AIT>::type areg;
+    typename FVec<8 * NIT>::type xreg;
 
 #define LOAD_A(S_)                                                                                \
     {                                                                                             \
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void conv_nn_x3_kernel(ConvNNArgs a) {
                 float f[8];                                                                       \
                 _Pragma("unroll") for (int r = 0; r < 8; ++r) f[r] = xreg[8 * it + r];            \
                 u32x4 hi, mid, lo;                                                                \
-                split8(f, hi, mid, lo);                                                           \
+                bm_split8_bf16<false>(f, hi, mid, lo);                                            \
                 Xs[(0 * XG + wave) * XW + xx] = hi;                                               \
                 Xs[(1 * XG + wave) * XW + xx] = mid;                                              \
                 Xs[(2 * XG + wave) * XW + xx] = lo;                                               \

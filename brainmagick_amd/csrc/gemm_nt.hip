@@ -15,7 +15,7 @@
 // The reduction domain is a flat list of (segment, 32-sample time chunk) pairs; `nsplit` workgroups
 // share one output tile (split-K) and write separate partial tiles that pack.hip's
 // bm_reduce_splits folds in a fixed order (deterministic).
-#include "bm_common.h"
+#include "mfma_split.h"
 
 #define BKT 32
 
@@ -28,8 +28,6 @@ struct GemmNTArgs {
     int S, M, Cn, T, dil, nsplit, G;
     int tiles_m, tiles_c;
 };
-
-template <int N> struct FVec { typedef float type __attribute__((ext_vector_type(N))); };
 
 // XWP = padded width of the staged X window (32 + 2*halo <= XWP), compile time so that the staging
 // registers can be a fixed-size vector.  The window is centred: it starts HP = (XWP-32)/2 samples
@@ -261,9 +259,6 @@ static int launch_gemm_nt(GemmNTArgs a, hipStream_t stream) {
     if (halo <= 32) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 96>(a, stream);
     return bm_set_error(BM_ERR_UNSUPPORTED, "gemm_nt: (kernel_size/2)*dilation = %d exceeds the 32-sample halo", halo);
 }
-
-// Picks the tile (128 or 64 rows / cols) with the least padding.
-static inline bool prefer_big(int n) { return (long)cdiv(n, 128) * 128 <= (long)cdiv(n, 64) * 64; }
 
 // Suggested split count so that the launch has ~>= 4 workgroups per CU.
 extern "C" int bm_gemm_nt_suggest_splits(int M, int Cn, int KS, int S, int T, int G) {

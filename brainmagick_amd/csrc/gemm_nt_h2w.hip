@@ -25,24 +25,21 @@
 //     early fragments of stage k + 1 under the last term (hi*lo).
 // Operand fragments roll through one register set: a term's fragments are replaced by those of the next k-step
 // as soon as its MFMAs are issued, so every LDS read is covered by the 15 MFMAs of the term in front of its use.
-// The loads are compiler-visible raw buffer loads: gemm_nt_x3w.hip hides its loads in inline asm with hand-counted
-// waits, which is only sound while the register allocator never copies a register whose load is still in
-// flight -- it did here (v_mov of a staging set ahead of its wait).  hipcc's own waits are conservative around the
-// interior / edge branch of the fetch; with one wait per stage, placed where every outstanding load is at least
-// half a stage old, conservative costs nothing.
+// The loads are compiler-visible raw buffer loads: loads hidden in inline asm with hand-counted waits (the wide
+// 3 x bf16 kernels that round 4 removed had them) are only sound while the register allocator never copies a
+// register whose load is still in flight -- it did here (v_mov of a staging set ahead of its wait).  hipcc's own
+// waits are conservative around the interior / edge branch of the fetch; with one wait per stage, placed where
+// every outstanding load is at least half a stage old, conservative costs nothing.
 // Rows past M / Cn are addressed through the per-lane offset, which the buffer descriptor range-checks: they
 // read as zeros and are never written, so M and Cn may be padded.
 // LDS (16-byte slots = 8 samples of one plane), two stage buffers of two planes each:
 //   A [4 groups of 8 samples][64 MW + 2 rows], X [NS slots][4 groups][64 + 2 rows]   (row counts = 2 mod 8: the
 //   16 lanes of a ds_write_b64 group -- 2 rows x 8 pieces -- land on 16 different bank pairs).
 #include <cstdlib>
-#include <utility>
-#include <cstring>
-#include "bm_common.h"
+#include "mfma_split.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #define HG_K 32                               // samples per stage
@@ -62,30 +59,8 @@ struct GemmNTArgsH {
     const int* order; const int* seg;
 };
 
-// same scale rule as conv_nn_h2w.hip: power of two s with amax * s in [2^14, 2^15), exact inverse
-__device__ __forceinline__ void hg_scale_from_amax(float amax, float& s, float& inv) {
-    const unsigned e = (__float_as_uint(amax) >> 23) & 0xffu;
-    int se = 127;
-    if (e != 0u && e != 255u) {
-        se = 268 - (int)e;
-        se = se > 253 ? 253 : (se < 1 ? 1 : se);
-    }
-    s = __uint_as_float((unsigned)se << 23);
-    inv = __uint_as_float((unsigned)(254 - se) << 23);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t hg_rsrc(const float* p, int bytes) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
 // Staging loads are compiler-visible raw buffer loads (hipcc counts them and places exact vmcnt(N) waits at
-// the first use of each register set).  gemm_nt_x3w.hip hides its loads in inline asm with hand-counted waits;
-// that is only sound while the register allocator never copies a register whose load is still in flight, which
-// it does here as soon as the schedule changes (observed: v_mov of a staging set ahead of its wait).
+// the first use of each register set); why not inline asm: see the head of this file.
 __device__ __forceinline__ u32x4 hg_ld128(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
 }
@@ -107,18 +82,7 @@ __device__ __forceinline__ void hg_split_store4(const float (&f)[4], float s, ch
     *reinterpret_cast<u32x2*>(dst + plane_bytes) = __builtin_bit_cast(u32x2, l);
 }
 
-// two fp32 values -> scaled f16 pairs: hi = f16(x * s), lo = f16(x * s - hi) (the product is exact, s is a power
-// of two; the difference is exact in fp32), written straight into the halves of the packed results: 4 VALU
-__device__ __forceinline__ void hg_split_pair(float x0, float x1, float s0, float s1, unsigned& hi, unsigned& lo) {
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %5, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %5, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(hi), "=&v"(lo)
-        : "v"(x0), "v"(x1), "v"(s0), "v"(s1));
-}
-
-// the two halves of hg_split_pair as separate statements (2 VALU each): the main loop puts them behind different MFMAs
+// the two halves of bm_split_pair as separate statements (2 VALU each): the main loop puts them behind different MFMAs
 __device__ __forceinline__ void hg_split_hi(float x0, float x1, float s0, float s1, unsigned& hi) {
     asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
         "v_fma_mixhi_f16 %0, %2, %4, 0" : "=&v"(hi) : "v"(x0), "v"(x1), "v"(s0), "v"(s1));
@@ -156,15 +120,6 @@ __device__ __forceinline__ void hg_touch(u32x4 (&r)[NP]) {
     else
         asm volatile("" :: "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]),
                      "v"(r[8]), "v"(r[9]), "v"(r[10]), "v"(r[11]));
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void hg_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void hg_static_for(F&& f) {
-    hg_static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 #ifdef HG_TRACE
@@ -241,8 +196,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
     const int a_bytes = (int)(((FL ? (long)(a.S - 1) * a.a_sstride : 0) + (long)(a.M - 1) * a.a_rstride + a.T) * 4);
     const int x_bytes = (int)(((FL ? (long)(a.S - 1) * a.x_sstride : 0) + (long)(a.Cn - 1) * a.x_rstride + a.T) * 4);
     float sa, sa_inv, sx, sx_inv;
-    hg_scale_from_amax(bm_amax_load(a.a_amax), sa, sa_inv);
-    hg_scale_from_amax(bm_amax_load(a.x_amax), sx, sx_inv);
+    bm_scale_from_amax(bm_amax_load(a.a_amax), sa, sa_inv);
+    bm_scale_from_amax(bm_amax_load(a.x_amax), sx, sx_inv);
 
     // The pieces of this thread: lane -> (row32 = tid >> 3, piece pl = tid & 7 of the 32 samples).  A piece i:
     // row m0 + 32 i + row32.  X piece (j, u) = index NA + 2 j + u: row c0 + 32 u + row32 read at tap shift
@@ -284,7 +239,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
         for (int i = 0; i < NA; ++i) {
             const int m = m0 + 32 * i + row32;
             float inv_unused;
-            hg_scale_from_amax(m < a.M ? a.a_row_amax[m] : 0.f, sarow[i], inv_unused);
+            bm_scale_from_amax(m < a.M ? a.a_row_amax[m] : 0.f, sarow[i], inv_unused);
         }
     }
     // (T0_ = first sample of the chunk in the staging set, local to its segment; FL: this lane's piece may already
@@ -306,8 +261,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
     int ld_c = FL ? 0 : (int)(q_begin - (long)ld_s * cps);
     // segment descriptors, rebuilt only when the cursor enters a new segment (FL: the whole tensors, once)
     const int seg0 = (FL || nst <= 0) ? 0 : HG_SEG(ld_s);
-    __amdgpu_buffer_rsrc_t qa = hg_rsrc(a.a + (long)seg0 * a.a_sstride, a_bytes);
-    __amdgpu_buffer_rsrc_t qx = hg_rsrc(a.x + (long)seg0 * a.x_sstride, x_bytes);
+    __amdgpu_buffer_rsrc_t qa = bm_buffer_rsrc(a.a + (long)seg0 * a.a_sstride, a_bytes);
+    __amdgpu_buffer_rsrc_t qx = bm_buffer_rsrc(a.x + (long)seg0 * a.x_sstride, x_bytes);
     int vn, vx[NXS];                                   // byte offset of the chunk to fetch (X: per tap)
     unsigned vna = 0;                                  // RS: the same for A, out of range when this lane's piece lies past T
     // FL: this lane's piece of the chunk at the cursor -- segment ls, local time lt (a multiple of 4), byte offsets
@@ -348,8 +303,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
         } else if (++ld_c == cps) {                                                               \
             ld_c = 0; ++ld_s;                                                                     \
             const int sg_ = HG_SEG(ld_s);                                                         \
-            qa = hg_rsrc(a.a + (long)sg_ * a.a_sstride, a_bytes);                                 \
-            qx = hg_rsrc(a.x + (long)sg_ * a.x_sstride, x_bytes);                                 \
+            qa = bm_buffer_rsrc(a.a + (long)sg_ * a.a_sstride, a_bytes);                              \
+            qx = bm_buffer_rsrc(a.x + (long)sg_ * a.x_sstride, x_bytes);                              \
         }                                                                                         \
     }
     // fetch of piece I_ of the chunk at the cursor: the whole offset travels in the per-lane address, which the
@@ -376,8 +331,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
     // consecutive MFMAs: split of samples 0-1, of samples 2-3, two 8-byte LDS writes (+ the fetch that refills it)
 #define HG_SV(I_) ((I_) < NA ? sva : svx[KS == 3 ? (HG_Q(I_) >> 1) % NXS : 0])
 #define HG_S(I_, R_) ((RS && (I_) < NA) ? sarow[(RS && (I_) < NA) ? (I_) : 0] : HG_SV(I_)[R_])
-#define HG_SPLIT0(I_) hg_split_pair(__uint_as_float(rp[I_][0]), __uint_as_float(rp[I_][1]), HG_S(I_, 0), HG_S(I_, 1), ph[0], pw[0]);
-#define HG_SPLIT1(I_) hg_split_pair(__uint_as_float(rp[I_][2]), __uint_as_float(rp[I_][3]), HG_S(I_, 2), HG_S(I_, 3), ph[1], pw[1]);
+#define HG_SPLIT0(I_) bm_split_pair(__uint_as_float(rp[I_][0]), __uint_as_float(rp[I_][1]), HG_S(I_, 0), HG_S(I_, 1), ph[0], pw[0]);
+#define HG_SPLIT1(I_) bm_split_pair(__uint_as_float(rp[I_][2]), __uint_as_float(rp[I_][3]), HG_S(I_, 2), HG_S(I_, 3), ph[1], pw[1]);
 #define HG_WRITE(I_, WB_)                                                                         \
     {                                                                                             \
         char* dst_ = (WB_) + ((I_) < NA ? ldsa + (I_) * 32 * 16                                   \
@@ -465,7 +420,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
             // (measured with the cycle trace of scripts/trace_wgrad.py: 16 fetches issued back to back block the
             // wavefront for 2 000 cycles).  Fragments roll through one register set: each is re-read for the next
             // k-step right behind the last MFMA that uses it.
-            hg_static_for<6 * TN>([&](auto nc) __attribute__((always_inline)) {
+            bm_static_for<6 * TN>([&](auto nc) __attribute__((always_inline)) {
                 constexpr int n = decltype(nc)::value;
                 constexpr int term = n / TN, w = n % TN, mt = w / NS, j = w % NS;
                 constexpr int pa = term % 3 == 0 ? 1 : 0, pb = term % 3 == 2 ? 1 : 0;
@@ -483,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
                 if constexpr (term == 0 && j == NS - 1 && w >= MW + NS) HG_READ_A1(1, rb, 1, mt)   // A.lo: last use
                 if constexpr (term == 1 && w == TN - 1) {
                     // A.lo fragments whose slot was taken by the late reads above
-                    hg_static_for<MW>([&](auto mc) __attribute__((always_inline)) {
+                    bm_static_for<MW>([&](auto mc) __attribute__((always_inline)) {
                         constexpr int m2 = decltype(mc)::value;
                         if constexpr (m2 * NS + NS - 1 < MW + NS) HG_READ_A1(1, rb, 1, m2)
                     });
@@ -502,7 +457,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
                 if constexpr (n < 5 * TN) {
                     constexpr int NSUB = 5 * NP, NSL = 5 * TN;
                     constexpr int q0 = (n * NSUB + NSL - 1) / NSL, q1 = ((n + 1) * NSUB + NSL - 1) / NSL;
-                    hg_static_for<q1 - q0>([&](auto qc) __attribute__((always_inline)) {
+                    bm_static_for<q1 - q0>([&](auto qc) __attribute__((always_inline)) {
                         constexpr int q = q0 + decltype(qc)::value, p = q / 5, sub = q % 5;
                         if constexpr (sub < 4) HG_SPLIT_SUB(p, sub)
                         else {
@@ -559,7 +514,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_h2w_kernel(GemmNTArgsH a) {
         __syncthreads();
         for (int i = tid; i < BM; i += 256) {
             float s_unused, inv_m = 0.f;
-            if (m0 + i < a.M) hg_scale_from_amax(a.a_row_amax[m0 + i], s_unused, inv_m);
+            if (m0 + i < a.M) bm_scale_from_amax(a.a_row_amax[m0 + i], s_unused, inv_m);
             smem[i] = inv_m;
         }
         __syncthreads();

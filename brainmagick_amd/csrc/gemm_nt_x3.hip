@@ -9,10 +9,7 @@
 // both the row-per-lane ds_read_b128 of the MFMA operands and the 8-lane ds_write_b128 groups of the
 // staging pass are bank-conflict free (a +1 pad slot made the writes 2-way); three planes per operand, one pre-shifted copy of the X tile per tap (as in
 // gemm_nt_bf16.hip).  Software pipeline, split-K, grouping and XCD mapping as in gemm_nt.hip.
-#include "bm_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_split.h"
 
 #define BKT2 32
 #define SLOTS 4          // 4 data slots per row, XOR-swizzled: slot (row, q) lives at row*4 + (q ^ ((row >> 2) & 3))
@@ -28,33 +25,6 @@ struct GemmNTArgsX {
     int S, M, Cn, T, dil, nsplit, G;
     int tiles_m, tiles_c;
 };
-
-template <int N> struct FVecD { typedef float type __attribute__((ext_vector_type(N))); };
-
-// exact 3-way split of 8 fp32 values into bf16 planes (hi, mid, lo)
-__device__ __forceinline__ void split8x(const float* f, u32x4& hi, u32x4& mid, u32x4& lo) {
-    bf16x8 h, m, l;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a = (__bf16)f[i];
-        const float r1 = f[i] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        h[i] = a; m[i] = b; l[i] = (__bf16)(r1 - (float)b);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    mid = __builtin_bit_cast(u32x4, m);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
-// wave-uniform buffer descriptor over one segment: out-of-range dwords (rows past the end, t < 0 on the
-// first row) read as 0 without any per-lane predicate
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t seg_rsrc(const float* p, int bytes) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 template <int WM, int WC, int MT, int NT, int KS>
 __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gemm_nt_x3_kernel(GemmNTArgsX a) {
@@ -103,8 +73,8 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][k][j][r] = 0.f;
 
-    typename FVecD<8 * AIT>::type areg;
-    typename FVecD<8 * XIT>::type xreg;
+    typename FVec<8 * AIT>::type areg;
+    typename FVec<8 * XIT>::type xreg;
 
     // per-thread element offsets inside a segment (row * stride + 8 * slot), fixed for the whole kernel
     int a_off[AIT], x_off[XPT];
@@ -147,8 +117,8 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
         const int t0 = ld_c * BKT2;                                                               \
         int sidx = s_begin + ld_s;                                                                \
         if (a.order) sidx = a.order[sidx];                                                        \
-        const __amdgpu_buffer_rsrc_t ra = seg_rsrc(a.a + (long)sidx * a.a_sstride, a_bytes);      \
-        const __amdgpu_buffer_rsrc_t rx = seg_rsrc(a.x + (long)sidx * a.x_sstride, x_bytes);      \
+        const __amdgpu_buffer_rsrc_t ra = bm_buffer_rsrc(a.a + (long)sidx * a.a_sstride, a_bytes);\
+        const __amdgpu_buffer_rsrc_t rx = bm_buffer_rsrc(a.x + (long)sidx * a.x_sstride, x_bytes);\
         if (t0 - halo < 0 || t0 + BKT2 + halo > a.T) {                                            \
             _Pragma("unroll") for (int i = 0; i < AIT; ++i)                                       \
                 LOAD8E(areg, 8 * i, ra, a_off[i] + t0, t0 + 8 * ((tid + i * NTH) & 3))            \
@@ -175,7 +145,7 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
             float f[8];                                                                           \
             _Pragma("unroll") for (int r = 0; r < 8; ++r) f[r] = areg[8 * i + r];                 \
             u32x4 hi, mid, lo;                                                                    \
-            split8x(f, hi, mid, lo);                                                              \
+            bm_split8_bf16<true>(f, hi, mid, lo);                                                 \
             const int slot = SWZ(e >> 2, e & 3);                                                  \
             As[slot] = hi; As[BM * SLOTS + slot] = mid; As[2 * BM * SLOTS + slot] = lo;           \
         }                                                                                         \
@@ -185,7 +155,7 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
                 float f[8];                                                                       \
                 _Pragma("unroll") for (int r = 0; r < 8; ++r) f[r] = xreg[8 * (j * XPT + i) + r]; \
                 u32x4 hi, mid, lo;                                                                \
-                split8x(f, hi, mid, lo);                                                          \
+                bm_split8_bf16<true>(f, hi, mid, lo);                                             \
                 const int slot = j * BC * SLOTS + SWZ(e >> 2, e & 3);                             \
                 Xs[slot] = hi; Xs[KS * BC * SLOTS + slot] = mid; Xs[2 * KS * BC * SLOTS + slot] = lo; \
             }                                                                                     \
@@ -290,8 +260,6 @@ extern "C" int bm_gemm_nt(const float* a, long a_sstride, long a_rstride, const 
                           long x_rstride, const int* order, const int* seg, float* part, int S, int G, int M,
                           int Cn, int T, int KS, int dil, int nsplit, void* stream);   // gemm_nt.hip
 
-static inline bool prefer_big_x(int n) { return (long)cdiv(n, 128) * 128 <= (long)cdiv(n, 64) * 64; }
-
 // Same contract as bm_gemm_nt (fp32 partial tiles out); fp32-accurate 3-plane bf16 emulation.
 extern "C" int bm_gemm_nt_x3(const float* a, long a_sstride, long a_rstride, const float* x,
                                long x_sstride, long x_rstride, const int* order, const int* seg,
@@ -312,9 +280,9 @@ extern "C" int bm_gemm_nt_x3(const float* a, long a_sstride, long a_rstride, con
     g.order = order; g.seg = seg; g.part = part;
     g.S = S; g.M = M; g.Cn = Cn; g.T = T; g.dil = dil; g.nsplit = nsplit; g.G = G;
     hipStream_t s = (hipStream_t)stream;
-    const bool bigM = prefer_big_x(M);
+    const bool bigM = prefer_big(M);
     if (KS == 1) {
-        const bool bigC = prefer_big_x(Cn);
+        const bool bigC = prefer_big(Cn);
         if (bigM && bigC) return launch_gemm_nt_x3<2, 2, 2, 2, 1>(g, s);
         if (bigM) return launch_gemm_nt_x3<2, 2, 2, 1, 1>(g, s);
         if (bigC) return launch_gemm_nt_x3<2, 2, 1, 2, 1>(g, s);

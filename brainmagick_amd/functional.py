@@ -249,7 +249,7 @@ class ChannelMergerFn(torch.autograd.Function):
         emb = H.fourier_emb(positions_u, D)
         seg = _arange_i32(U + 1, meg.device)
         scores = H.gemm_nt(heads, emb, U, O, C, D, a_strides=(O * D if per_layout_heads else 0, D),
-                           x_strides=(C * D, D), seg=seg, G=U, force_f32=True).view(U, O, C)
+                           x_strides=(C * D, D), seg=seg, G=U).view(U, O, C)
         weights = H.masked_softmax(scores, positions_u, ban_center, ban_radius)
         widx = H.index_i32(_c(layout_index.to(torch.int64)), U)
         wp = H.pack_weights(weights, U, O, C, 1, O * C, C, 1, 0, shape=(meg.shape[2], 1))
@@ -314,7 +314,7 @@ class FusedFrontEndFn(torch.autograd.Function):
         emb = H.fourier_emb(positions_u, Dp)
         seg_u = _arange_i32(U + 1, dev)
         scores = H.gemm_nt(heads, emb, U, O, C, Dp, a_strides=(0, Dp), x_strides=(C * Dp, Dp), seg=seg_u,
-                           G=U, force_f32=True).view(U, O, C)
+                           G=U).view(U, O, C)
         wm = H.masked_softmax(scores, positions_u, ban_center, ban_radius)              # [U, O, C]
         # P[u] = W1 Wm[u], with b1 as column C
         _, p, _ = H.conv_nn(wm, H.pack_conv_fwd(w1), L, 1, 1)                           # [U, L, C]
@@ -400,7 +400,7 @@ def _clip_raw_scores(estimate, candidate, B, Bc, K):
     for r0, rows in blocks:
         blk = H.share_amax(candidate, cand2[r0:r0 + rows])
         H.gemm_nt(estimate, blk, 1, B, rows, K, 1, 1, a_strides=(0, K), x_strides=(0, K),
-                  out=raw.view(-1)[r0:], out_strides=(0, Bc, 1, 0), force_f32=True)
+                  out=raw.view(-1)[r0:], out_strides=(0, Bc, 1, 0))
     return raw
 
 

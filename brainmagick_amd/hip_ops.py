@@ -83,6 +83,7 @@ class KernelTimer:
 
 
 _timer: tp.Optional[KernelTimer] = None
+_MODE_SUFFIX = {"f32": "", "f32x3": "_x3", "f16x2": "_h2w"}      # compute mode -> kernel family in the timer's labels
 
 
 def set_kernel_timer(timer: tp.Optional[KernelTimer]):
@@ -118,6 +119,24 @@ def conv_mpad(M: int) -> int:
     return lib().bm_conv_mpad(M)
 
 
+# A value that a kernel derived from a tensor's contents (its maximum, per-channel maxima, inverse row norms) is
+# remembered ON the tensor as (version, data_ptr, value[, checked]); it holds for exactly those contents.
+def _note(t: torch.Tensor, attr: str, value, *checked):
+    try:
+        setattr(t, attr, (t._version, t.data_ptr(), value) + checked)
+    except Exception:       # tensors that refuse attributes: just do not cache
+        pass
+
+
+def _noted(t: torch.Tensor, attr: str, need_checked: bool = False):
+    """The value noted on ``t`` if it still describes it, else None.  ``need_checked``: only a note taken together
+    with the non-finite check will do."""
+    note = getattr(t, attr, None)
+    if note is not None and note[0] == t._version and note[1] == t.data_ptr() and (not need_checked or note[3]):
+        return note[2]
+    return None
+
+
 AMAX_SHARDS = 8       # an amax slot is 8 floats (csrc/bm_common.h; the finalize kernels write all eight); max|x| = slot.max()
 amax_scans = 0        # number of stand-alone amax passes launched (producers that publish their own maximum need none)
 
@@ -127,20 +146,16 @@ def amax(x: torch.Tensor, nonfinite_flag: tp.Optional[torch.Tensor] = None) -> t
     its version counter, so a tensor consumed by several contractions (forward conv, weight gradient) is
     scanned once and an in-place modification invalidates the cache.  ``nonfinite_flag`` (int32 device tensor):
     element 0 is set to 1 by the same pass if x holds an inf / nan (a cached tensor was checked when it was scanned)."""
-    cached = getattr(x, "_bm_amax", None)
-    if cached is not None and cached[0] == x._version and cached[1] == x.data_ptr() and \
-            (nonfinite_flag is None or cached[3]):
-        return cached[2]
+    cached = _noted(x, "_bm_amax", nonfinite_flag is not None)
+    if cached is not None:
+        return cached
     _req(x, "amax.x")
     global amax_scans
     amax_scans += 1
     out = torch.empty(AMAX_SHARDS, device=x.device, dtype=torch.float32)
     check(lib().bm_amax_checked(_p(x), x.numel(), _p(out), _p(_amax_ws(x.device)),
                                 _p(_opt(nonfinite_flag, "nonfinite_flag", torch.int32)), _stream()), "bm_amax")
-    try:
-        x._bm_amax = (x._version, x.data_ptr(), out, nonfinite_flag is not None)
-    except Exception:       # tensors that refuse attributes: just do not cache
-        pass
+    _note(x, "_bm_amax", out, nonfinite_flag is not None)
     return out
 
 
@@ -170,7 +185,7 @@ def _amax_slot(t: torch.Tensor) -> tp.Optional[torch.Tensor]:
         pool = _amax_pool[t.device] = [torch.zeros(4096 * AMAX_SHARDS, device=t.device, dtype=torch.float32), 0]
     slot = pool[0][pool[1]:pool[1] + AMAX_SHARDS]
     pool[1] += AMAX_SHARDS
-    t._bm_amax = (t._version, t.data_ptr(), slot, False)
+    _note(t, "_bm_amax", slot, False)
     return slot
 
 
@@ -182,15 +197,12 @@ def _row_amax_out(t: torch.Tensor, slot) -> tp.Optional[torch.Tensor]:
     if slot is None:
         return None
     rows = torch.empty(t.shape[1], device=t.device, dtype=torch.float32)
-    t._bm_row_amax = (t._version, t.data_ptr(), rows)
+    _note(t, "_bm_row_amax", rows)
     return rows
 
 
 def row_amax_of(t: torch.Tensor) -> tp.Optional[torch.Tensor]:
-    cached = getattr(t, "_bm_row_amax", None)
-    if cached is not None and cached[0] == t._version and cached[1] == t.data_ptr():
-        return cached[2]
-    return None
+    return _noted(t, "_bm_row_amax")
 
 
 def _slot_args(slot):
@@ -215,11 +227,7 @@ def share_amax(src: torch.Tensor, view: torch.Tensor) -> torch.Tensor:
     f16 headroom serves as the scale), so the slice needs no pass of its own."""
     if _compute_dtype != "f16x2":     # nobody consumes a maximum in the other compute modes: no scan
         return view
-    slot = amax(src)
-    try:
-        view._bm_amax = (view._version, view.data_ptr(), slot, False)
-    except Exception:
-        pass
+    _note(view, "_bm_amax", amax(src), False)
     return view
 
 
@@ -406,11 +414,10 @@ def conv_nn(x: torch.Tensor, wpacked: torch.Tensor, M: int, KS: int = 1, dil: in
             check(fn(_p(x), Cin * T, _p(wpacked), *common, _stream()), f"bm_conv1d_nn[{mode}]")
     if _timer is not None:
         if mode == "f16x2":
-            label = f"conv_nn_h2w_kernel<{KS},{lib().bm_conv_h2_mw_for(M)}>"
+            tile = f"{KS},{lib().bm_conv_h2_mw_for(M)}"
         else:
-            label = {"f32": f"conv_nn_kernel<{lib().bm_conv_mt_for(M)}>",
-                     "f32x3": f"conv_nn_x3_kernel<{lib().bm_conv_x3_mt_for(M)}>"}[mode]
-        _timer.launch(label, 2.0 * B * T * M * Cin * KS, launch)
+            tile = (lib().bm_conv_mt_for if mode == "f32" else lib().bm_conv_x3_mt_for)(M)
+        _timer.launch(f"conv_nn{_MODE_SUFFIX[mode]}_kernel<{tile}>", 2.0 * B * T * M * Cin * KS, launch)
     else:
         launch()
     return y_pre, y_out, stats
@@ -471,11 +478,8 @@ def group_by_index(idx: torch.Tensor, G: int):
 
 def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, KS: int = 1,
             dil: int = 1, a_strides=None, x_strides=None, order=None, seg=None, G: int = 1,
-            out: tp.Optional[torch.Tensor] = None, out_strides=None, nsplit: tp.Optional[int] = None,
-            force_f32: bool = False):
+            out: tp.Optional[torch.Tensor] = None, out_strides=None, nsplit: tp.Optional[int] = None):
     """out[g*sg + m*sm + c*sc + j*sj] = sum_{s in g} sum_t a[s][m][t] * x[s][c][t + shift_j].
-
-    (``force_f32`` is kept in the signature for callers whose result feeds a softmax: every mode left is fp32-class.)
 
     a_strides / x_strides = (segment stride, row stride) in elements; defaults are contiguous
     [S][rows][T].  Default ``out`` is [G][M][Cn][KS] contiguous."""
@@ -545,8 +549,7 @@ def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, K
                      _p(_opt(order, "order", torch.int32)), _p(_opt(seg, "seg", torch.int32)), _p(part), S,
                      G, M, Cn, T, KS, dil, nsplit, _stream()), "bm_gemm_nt")
     if _timer is not None:
-        suffix = {"f32": "", "f32x3": "_x3", "f16x2": "_h2w"}[mode]
-        _timer.launch(f"gemm_nt{suffix}_kernel<KS={KS}>", 2.0 * S * T * M * Cn * KS, launch)
+        _timer.launch(f"gemm_nt{_MODE_SUFFIX[mode]}_kernel<KS={KS}>", 2.0 * S * T * M * Cn * KS, launch)
     else:
         launch()
     if part is not out:
@@ -630,8 +633,7 @@ def gemm_nt_partials(a, x, S, M, Cn, T, a_strides, x_strides, nsplit=None):
             check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1], None, None, _p(part),
                      S, 1, M, Cn, T, 1, 1, nsplit, _stream()), "bm_gemm_nt")
     if _timer is not None:
-        _timer.launch("clip_scores:gemm_nt" + {"f32": "", "f32x3": "_x3", "f16x2": "_h2w"}[mode],
-                      2.0 * S * T * M * Cn, launch)
+        _timer.launch("clip_scores:gemm_nt" + _MODE_SUFFIX[mode], 2.0 * S * T * M * Cn, launch)
     else:
         launch()
     return part
@@ -791,27 +793,22 @@ def clip_inv_norms(cand: torch.Tensor, nonfinite_flag: tp.Optional[torch.Tensor]
     a step needs from them: max |cand| (attached to the tensor like ``amax`` would, f16x2 mode) and -- with
     ``nonfinite_flag`` -- the reference's finiteness assert.  Cached on the tensor object together with its version
     counter: the Solver runs it when the batch arrives, ClipLoss finds the result."""
-    cached = getattr(cand, "_bm_inv_norms", None)
-    if cached is not None and cached[0] == cand._version and cached[1] == cand.data_ptr() and \
-            (nonfinite_flag is None or cached[3]):
-        return cached[2]
+    checked = nonfinite_flag is not None
+    cached = _noted(cand, "_bm_inv_norms", checked)
+    if cached is not None:
+        return cached
     _req(cand, "clip_inv_norms.cand")
     Bc = cand.shape[0]
     K = cand.numel() // max(Bc, 1)
     out = torch.empty(Bc, device=cand.device, dtype=torch.float32)
-    have = getattr(cand, "_bm_amax", None)
-    have = have is not None and have[0] == cand._version and have[1] == cand.data_ptr() and \
-        (nonfinite_flag is None or have[3])
+    have = _noted(cand, "_bm_amax", checked) is not None
     slot = None if have else _amax_slot(cand)            # None outside f16x2 mode
     check(lib().bm_clip_cand_prep(_p(cand), Bc, K, _p(out), _p(slot),
                                   _p(_opt(nonfinite_flag, "nonfinite_flag", torch.int32)), _stream()),
           "bm_clip_cand_prep")
     if slot is not None:
-        cand._bm_amax = (cand._version, cand.data_ptr(), slot, nonfinite_flag is not None)
-    try:
-        cand._bm_inv_norms = (cand._version, cand.data_ptr(), out, nonfinite_flag is not None)
-    except Exception:
-        pass
+        _note(cand, "_bm_amax", slot, checked)
+    _note(cand, "_bm_inv_norms", out, checked)
     return out
 
 
