@@ -172,6 +172,101 @@ class ConvBNActFn(torch.autograd.Function):
         return (dx, dw, dbias, dgamma, dbeta) + (None,) * 10
 
 
+def _strided_forward(x, weight, transposed, stride, dil, pad, **kw):
+    """The layer's forward kernel: gather form for nn.Conv1d [M, Cin, KS], scatter form for nn.ConvTranspose1d
+    [Cin, M, KS] (csrc/conv_strided.hip)."""
+    KS = weight.shape[2]
+    M = weight.shape[1] if transposed else weight.shape[0]
+    Tout = H.conv_out_len(x.shape[2], KS, stride, dil, pad, transposed)
+    wp = H.pack_strided_rows_second(weight) if transposed else H.pack_strided_rows_first(weight)
+    return H.conv_strided(x, wp, M, Tout, KS, stride, dil, pad, transposed, **kw)
+
+
+def _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad):
+    """(dx, dw) of a strided / transposed layer: the data gradient is the OTHER form at the layer's input length, the
+    weight gradient one kernel with the operand roles swapped."""
+    KS = weight.shape[2]
+    dw = None
+    if ctx.needs_input_grad[1]:
+        dst = H.grad_destination(weight)
+        a, xl = (x, dy) if transposed else (dy, x)
+        dw = H.conv_strided_wgrad(a, xl, KS, stride, dil, pad, out=dst)
+        dw = dw.view(weight.shape)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        Cin, T = x.shape[1], x.shape[2]
+        # rows of the data gradient = the layer's input channels: dim 0 of a transposed weight, dim 1 of a Conv1d one
+        wp = H.pack_strided_rows_first(weight) if transposed else H.pack_strided_rows_second(weight)
+        _, dx, _ = H.conv_strided(dy, wp, Cin, T, KS, stride, dil, pad, not transposed)
+    return dx, dw
+
+
+class StridedConv1dFn(torch.autograd.Function):
+    """nn.Conv1d with any stride / kernel / padding, or nn.ConvTranspose1d (``transposed``), + bias [+ activation]
+    (bm/models/common.py:96, 112-114 for layers without BatchNorm)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride: int, dil: int, pad: int, act: int, leak: float, transposed: bool):
+        x, weight = _c(x), _c(weight)
+        need_pre = act != H.ACT_NONE and (x.requires_grad or weight.requires_grad)
+        pre, out, _ = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, act=act, leak=leak,
+                                       want_pre=need_pre)
+        ctx.save_for_backward(x, weight, pre)
+        ctx.cfg = (stride, dil, pad, act, leak, transposed, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, pre = ctx.saved_tensors
+        stride, dil, pad, act, leak, transposed, has_bias = ctx.cfg
+        dout = _c(dout)
+        dbias = None
+        if act != H.ACT_NONE:
+            dy, _, _, dbias = H.act_bn_bwd(dout, pre, None, None, None, None, False, act, leak, want_dbias=has_bias)
+        else:
+            dy = dout
+            if has_bias:
+                dbias = H.channel_sum(dy)
+        dx, dw = _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad)
+        return (dx, dw, dbias) + (None,) * 6
+
+
+class StridedConvBNActFn(torch.autograd.Function):
+    """The same layer followed by BatchNorm1d and the activation (bm/models/common.py:112-120).
+
+    train: the conv kernel writes the pre-activation and the per-tile sums / sums of squares -> bn_finalize (running
+    statistics updated like torch) -> affine_act_res.  eval: ONE launch with the affine and the activation in the
+    epilogue.  The BatchNorm kernels are ConvBNActFn's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, num_batches, training: bool,
+                stride: int, dil: int, pad: int, act: int, leak: float, transposed: bool, momentum: float, eps: float):
+        x, weight = _c(x), _c(weight)
+        needs_grad = x.requires_grad or weight.requires_grad
+        if training:
+            pre, _, stats = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, want_pre=True,
+                                             want_out=False, want_stats=True)
+            mean, invstd, scale, shift = H.bn_finalize(stats, pre.shape[0] * pre.shape[2], gamma, beta, running_mean,
+                                                       running_var, num_batches, momentum, eps)
+            out = H.affine_act_res(pre, scale, shift, None, act, leak)
+        else:
+            mean, invstd, scale, shift = H.bn_eval_affine(gamma, beta, running_mean, running_var, eps)
+            pre, out, _ = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, scale=scale, shift=shift,
+                                           act=act, leak=leak, want_pre=needs_grad)
+        ctx.save_for_backward(x, weight, pre, scale, shift, mean, invstd)
+        ctx.cfg = (training, stride, dil, pad, act, leak, transposed, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, pre, scale, shift, mean, invstd = ctx.saved_tensors
+        training, stride, dil, pad, act, leak, transposed, has_bias = ctx.cfg
+        dy, dgamma, dbeta, dbias = H.act_bn_bwd(_c(dout), pre, scale, shift, mean, invstd, training, act, leak,
+                                                want_affine_grads=True, want_dbias=has_bias)
+        dx, dw = _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad)
+        return (dx, dw, dbias, dgamma, dbeta) + (None,) * 12
+
+
 class GLUConvFn(torch.autograd.Function):
     """Conv1d(C -> 2C, k = 1 + 2*glu_context) followed by GLU(dim=1) (bm/models/common.py:133-138)."""
 

@@ -423,6 +423,107 @@ def conv_nn(x: torch.Tensor, wpacked: torch.Tensor, M: int, KS: int = 1, dil: in
     return y_pre, y_out, stats
 
 
+# ------------------------------------------------------------------------------------------------
+# Strided / transposed convs (csrc/conv_strided.hip): nn.Conv1d with stride, nn.ConvTranspose1d, their data and weight
+# gradients.  One kernel family, exact-fp32 MFMA, for all three compute modes (an f16x2 variant is a follow-up; the
+# timer labels below tell which family ran).
+def conv_out_len(T: int, KS: int, stride: int, dil: int, pad: int, transposed: bool) -> int:
+    """Output length of nn.Conv1d / nn.ConvTranspose1d (output_padding 0); raises like torch when there is none."""
+    Tout = lib().bm_conv1d_out_len(T, KS, stride, dil, pad, int(transposed))
+    if Tout < 1:
+        if transposed:
+            raise RuntimeError(f"ConvTranspose1d: input of {T} samples (kernel {KS}, stride {stride}, dilation {dil}, "
+                               f"padding {pad}) gives an output of {Tout} samples. Output size is too small")
+        raise RuntimeError(f"Calculated padded input size per channel: ({T + 2 * pad}). Kernel size: "
+                           f"({dil * (KS - 1) + 1}). Kernel size can't be greater than actual input size")
+    return Tout
+
+
+def pack_weights_f32(src: torch.Tensor, M: int, Cin: int, KS: int, sm: int, sc: int, sj: int) -> torch.Tensor:
+    """The fp32 packed layout [chunk][tap][16][Mpad] whatever the compute mode (rows m = src[m*sm + c*sc + j*sj])."""
+    _req(src, "pack_weights_f32.src")
+    dst = torch.empty(lib().bm_packed_weight_elems(1, M, Cin, KS), device=src.device, dtype=torch.float32)
+    check(lib().bm_pack_weights(_p(src), _p(dst), 1, M, Cin, KS, 0, sm, sc, sj, 0, None, _stream()), "bm_pack_weights")
+    return dst
+
+
+def pack_strided_rows_first(weight: torch.Tensor) -> torch.Tensor:
+    """[rows, reduced, KS] (nn.Conv1d's [M, Cin, KS] forward; nn.ConvTranspose1d's [Cin, M, KS] data gradient)."""
+    R, C, KS = weight.shape
+    return pack_weights_f32(weight, R, C, KS, C * KS, KS, 1)
+
+
+def pack_strided_rows_second(weight: torch.Tensor) -> torch.Tensor:
+    """[reduced, rows, KS] (nn.ConvTranspose1d's [Cin, M, KS] forward; nn.Conv1d's [M, Cin, KS] data gradient)."""
+    C, R, KS = weight.shape
+    return pack_weights_f32(weight, R, C, KS, KS, R * KS, 1)
+
+
+def conv_strided(x: torch.Tensor, wpacked: torch.Tensor, M: int, Tout: int, KS: int, stride: int, dil: int, pad: int,
+                 transposed: bool, bias=None, scale=None, shift=None, act: int = ACT_NONE, leak: float = 0.,
+                 want_pre: bool = False, want_out: bool = True, want_stats: bool = False):
+    """Gather form (``transposed=False``: strided nn.Conv1d) or scatter form (nn.ConvTranspose1d) of
+    csrc/conv_strided.hip on x [B, Cin, T] -> [B, M, Tout]; returns (y_pre | None, y_out | None, stats | None) like
+    ``conv_nn``.  ``Tout`` is the caller's (``conv_out_len`` forward, the layer's input length as a data gradient)."""
+    _req(x, "conv_strided.x")
+    _req(wpacked, "conv_strided.w")
+    B, Cin, T = x.shape
+    if Tout < 1:
+        raise RuntimeError(f"conv_strided: output length {Tout} < 1")
+    y_pre = torch.empty(B, M, Tout, device=x.device, dtype=torch.float32) if want_pre else None
+    y_out = torch.empty(B, M, Tout, device=x.device, dtype=torch.float32) if want_out else None
+    stats = None
+    if want_stats:
+        stats = torch.empty(lib().bm_conv_strided_stats_tiles(B, Tout, stride, int(transposed)), M, 2, device=x.device,
+                            dtype=torch.float32)
+    fn = lib().bm_conv1d_transposed if transposed else lib().bm_conv1d_strided
+    name = "conv_transposed_kernel" if transposed else "conv_strided_kernel"
+
+    def launch():
+        check(fn(_p(x), Cin * T, _p(wpacked), _p(_opt(bias, "bias")), _p(_opt(scale, "scale")), _p(_opt(shift, "shift")),
+                 _p(y_pre), _p(y_out), M * Tout, _p(stats), B, Cin, M, T, Tout, KS, stride, dil, pad, act, leak,
+                 _stream()), "bm_conv1d_transposed" if transposed else "bm_conv1d_strided")
+    if _timer is not None:
+        taps = KS if not transposed else -(-KS // stride)
+        _timer.launch(f"{name}<K={KS},s={stride}>", 2.0 * B * (Tout if not transposed else T * stride) * M * Cin * taps,
+                      launch)
+    else:
+        launch()
+    return y_pre, y_out, stats
+
+
+def conv_strided_wgrad(a: torch.Tensor, xl: torch.Tensor, KS: int, stride: int, dil: int, pad: int,
+                       out: tp.Optional[torch.Tensor] = None, nsplit: tp.Optional[int] = None) -> torch.Tensor:
+    """out[r][q][j] = sum_{b,u} a[b][r][u] * xl[b][q][u*stride + j*dil - pad]: a = dY, xl = x for the strided layer
+    (-> [M, Cin, KS]); a = x, xl = dY for the transposed one (-> [Cin, M, KS]).  Deterministic split-K."""
+    _req(a, "conv_strided_wgrad.a")
+    _req(xl, "conv_strided_wgrad.xl")
+    S, R, U = a.shape
+    S2, Q, L = xl.shape
+    assert S == S2, (a.shape, xl.shape)
+    if out is None:
+        out = torch.empty(R, Q, KS, device=a.device, dtype=torch.float32)
+    else:
+        _req(out, "conv_strided_wgrad.out")
+        assert out.numel() == R * Q * KS
+        _touched(out)
+    if nsplit is None:
+        nsplit = lib().bm_conv1d_strided_wgrad_suggest_splits(R, Q, KS, S, U)
+    part = out if nsplit == 1 else torch.empty(nsplit * R * Q * KS, device=a.device, dtype=torch.float32)
+
+    def launch():
+        check(lib().bm_conv1d_strided_wgrad(_p(a), R * U, _p(xl), Q * L, _p(part), S, R, Q, U, L, KS, stride, dil, pad,
+                                            nsplit, _stream()), "bm_conv1d_strided_wgrad")
+    if _timer is not None:
+        _timer.launch(f"conv_strided_wgrad_kernel<K={KS},s={stride}>", 2.0 * S * U * R * Q * KS, launch)
+    else:
+        launch()
+    if part is not out:
+        check(lib().bm_reduce_splits(_p(part), _p(out), 1, nsplit, R, Q, KS, R * Q * KS, Q * KS, KS, 1, _stream()),
+              "bm_reduce_splits")
+    return out
+
+
 # Device-side "index out of range" flag (one int32 per device).  The grouped kernels never read outside
 # their weight tables (bad indices are clamped to group 0 by bm_index_to_i32 / skipped by
 # bm_group_by_index); the flag is raised as an IndexError at the next synchronisation point the caller

@@ -111,7 +111,13 @@ class ConvSequence(nn.Module):
     ``dropout_input`` (nn.Dropout), ``rewrite`` (1x1 conv + LeakyReLU), ``scale`` (LayerScale) and ``post_skip``
     (a depthwise 1x1 conv without bias = one factor per channel) sit between the activation and the skip
     addition: a layer that has any of them runs the fused function without its residual, the extras as (GPU) torch
-    ops or the 1x1 HIP conv, and the addition as one streaming launch -- slower than the hot path, never an error."""
+    ops or the 1x1 HIP conv, and the addition as one streaming launch -- slower than the hot path, never an error.
+
+    A layer with ``stride == 1``, an odd kernel and ``decode=False`` (every layer SimpleConv builds) runs on the
+    "same"-padding kernels above.  Every other layer -- the reference's own defaults ``kernel=4, stride=2``, and
+    ``decode=True``, which builds ``nn.ConvTranspose1d`` modules like the reference (ConvRNN's decoder) -- runs on the
+    strided / transposed kernels (``BF.StridedConv1dFn`` / ``BF.StridedConvBNActFn``, csrc/conv_strided.hip); there
+    the skip addition follows the reference's rule ``x.shape == old_x.shape`` (common.py:146)."""
 
     def __init__(self, channels: tp.Sequence[int], kernel: int = 4, dilation_growth: int = 1,
                  dilation_period: tp.Optional[int] = None, stride: int = 2,
@@ -121,14 +127,6 @@ class ConvSequence(nn.Module):
                  activation_on_last: bool = True, post_skip: bool = False, glu: int = 0,
                  glu_context: int = 0, glu_glu: bool = True, activation: tp.Any = None) -> None:
         super().__init__()
-        unsupported = dict(stride=stride != 1, decode=decode)
-        bad = [k for k, v in unsupported.items() if v]
-        if bad:
-            raise NotImplementedError(
-                f"ConvSequence options {bad} are outside the MI355X hot path (unused by the paper's "
-                "grids, SURVEY.md §2.2)")
-        if kernel % 2 != 1:
-            raise NotImplementedError("only odd kernels ('same' padding) are on the hot path")
         dilation = 1
         channels = tuple(channels)
         self.skip = skip
@@ -137,10 +135,15 @@ class ConvSequence(nn.Module):
         if activation is None:
             activation = partial(_Activation, "leaky", leakiness)
         self._plan: tp.List[dict] = []
+        Conv = nn.Conv1d if not decode else nn.ConvTranspose1d
+        # layers outside stride 1 / odd kernel / Conv1d run on the strided family (csrc/conv_strided.hip)
+        strided = stride != 1 or kernel % 2 != 1 or decode
         for k, (chin, chout) in enumerate(zip(channels[:-1], channels[1:])):
             layers: tp.List[nn.Module] = []
             is_last = k == len(channels) - 2
             plan = dict(dilation=1, act=None, bn=None, glu=None, pre=None, post=[])
+            if dilation_growth > 1:
+                assert kernel % 2 != 0, "Supports only odd kernel with dilation for now"
             if k == 0 and dropout_input:
                 assert 0 < dropout_input < 1
                 layers.append(nn.Dropout(dropout_input))
@@ -148,9 +151,10 @@ class ConvSequence(nn.Module):
             if dilation_period and (k % dilation_period) == 0:
                 dilation = 1
             pad = kernel // 2 * dilation
-            layers.append(nn.Conv1d(chin, chout, kernel, 1, pad, dilation=dilation, groups=groups if k > 0 else 1))
+            layers.append(Conv(chin, chout, kernel, stride, pad, dilation=dilation, groups=groups if k > 0 else 1))
             plan["conv"] = layers[-1]
             plan["dilation"] = dilation
+            plan["strided"] = (stride, pad, decode) if strided else None
             dilation *= dilation_growth
             if activation_on_last or not is_last:
                 if batch_norm:
@@ -170,7 +174,7 @@ class ConvSequence(nn.Module):
                     layers.append(LayerScale(chout, scale))
                     plan["post"].append(("scale", layers[-1]))
                 if post_skip:
-                    layers.append(nn.Conv1d(chout, chout, 1, groups=chout, bias=False))
+                    layers.append(Conv(chout, chout, 1, groups=chout, bias=False))
                     plan["post"].append(("post_skip", layers[-1]))
             self.sequence.append(nn.Sequential(*layers))
             if glu and (k + 1) % glu == 0:
@@ -209,6 +213,36 @@ class ConvSequence(nn.Module):
                 outs.append(BF.Conv1dFn.apply(xg, w, b, plan["dilation"], code, leak, False))
         return torch.cat(outs, dim=1)
 
+    def _strided_layer(self, x, plan, code, leak):
+        """A layer with a stride, an even kernel or ``decode`` (nn.ConvTranspose1d): conv [-> BatchNorm] -> activation
+        on the strided / transposed kernels.  ``groups`` > 1 as in ``_grouped_layer``: independent layers on channel
+        slices; nn.ConvTranspose1d keeps its weight as [in, out / groups, K], so a group is a slice of INPUT channels
+        there and of output channels in nn.Conv1d."""
+        conv, bn = plan["conv"], plan["bn"]
+        stride, pad, decode = plan["strided"]
+        G = conv.groups
+        cin, cout = conv.in_channels // G, conv.out_channels // G
+        outs = []
+        count0 = bn.num_batches_tracked.clone() if bn is not None and G > 1 else None
+        for g in range(G):
+            if G == 1:
+                xg, w, b, sl = x, conv.weight, conv.bias, None
+            else:
+                xg = x[:, g * cin:(g + 1) * cin].contiguous()
+                w = conv.weight[g * cin:(g + 1) * cin] if decode else conv.weight[g * cout:(g + 1) * cout]
+                b = conv.bias[g * cout:(g + 1) * cout] if conv.bias is not None else None
+                sl = slice(g * cout, (g + 1) * cout)
+            if bn is not None:
+                bnp = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if sl is None else \
+                    (bn.weight[sl], bn.bias[sl], bn.running_mean[sl], bn.running_var[sl])
+                count = bn.num_batches_tracked if g == G - 1 else count0.clone()   # the module's counter moves once, last
+                outs.append(BF.StridedConvBNActFn.apply(
+                    xg, w, b, *bnp, count, self.training, stride, plan["dilation"], pad, code, leak, decode,
+                    bn.momentum, bn.eps))
+            else:
+                outs.append(BF.StridedConv1dFn.apply(xg, w, b, stride, plan["dilation"], pad, code, leak, decode))
+        return outs[0] if G == 1 else torch.cat(outs, dim=1)
+
     def forward(self, x: tp.Any) -> tp.Any:
         for module_idx, module in enumerate(self.sequence):
             plan = self._plan[module_idx]
@@ -221,7 +255,12 @@ class ConvSequence(nn.Module):
             if plan["pre"] is not None:
                 x = plan["pre"](x)                                  # nn.Dropout on the input of the sequence
             fused_residual = residual and not plan["post"] and plan["pre"] is None
-            if conv.groups != 1:
+            if plan["strided"] is not None:
+                x = self._strided_layer(x, plan, code, leak)
+                # the addition is decided below, once the extras have run, by the reference's shape rule
+                # (common.py:146): with a stride or an even kernel equal channel counts do not mean equal lengths
+                fused_residual = False
+            elif conv.groups != 1:
                 x = self._grouped_layer(x, plan, code, leak, fused_residual)
             elif plan["bn"] is not None:
                 bn = plan["bn"]
@@ -240,6 +279,8 @@ class ConvSequence(nn.Module):
                     x = op[1](x)
                 else:                                               # depthwise 1x1 without bias: one factor per channel
                     x = x * op[1].weight.view(1, -1, 1)
+            if plan["strided"] is not None:
+                residual = self.skip and x.shape == old_x.shape
             if residual and not (fused_residual and plan["bn"] is not None):
                 x = _AddFn.apply(x if x.is_contiguous() else x.contiguous(), old_x)
             glu = self.glus[module_idx]

@@ -7,7 +7,8 @@ Options the paper's grids never use are either implemented off the hot path (GPU
 functions: ``dropout``, ``conv_dropout``, ``dropout_input``, ``scale``, ``rewrite``, ``post_skip``, ``merger_penalty``,
 ``merger_per_subject``, ``groups``, more inputs than ``meg`` with or without ``concatenate``) or raise
 ``NotImplementedError`` at construction time (``n_fft``).  ``dual_path`` runs torch's GPU LSTM
-between the stack and the head.
+between the stack and the head.  SimpleConv always builds its stacks with ``stride=1`` and asserts an odd kernel; the
+strided, even-kernel and ``decode`` layers that ``ConvSequence`` also accepts are not reachable from here.
 """
 import random
 import typing as tp

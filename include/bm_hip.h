@@ -61,6 +61,38 @@ int bm_conv1d_nn(const float* x, long x_bstride, const float* wpacked, const int
                  long res_bstride, float* y_pre, float* y_out, long y_bstride, float* stats, int B,
                  int Cin, int M, int T, int KS, int dil, int act, float leak, void* stream);
 
+/* ---- strided / transposed conv, fp32 MFMA (conv_strided.hip)  bm/models/common.py:96, 112-114 ----
+ * The reference's ConvSequence defaults (kernel 4, stride 2) and its decoder (`decode=True`: nn.ConvTranspose1d).
+ * General in KS >= 1 (even kernels included), stride >= 1, dil >= 1, pad >= 0; exact-fp32 MFMA in every compute mode.
+ *   bm_conv1d_strided     y[b][m][u] = ep(bias[m] + sum_{c,j} W[m][c][j] * x[b][c][u*stride + j*dil - pad])
+ *   bm_conv1d_transposed  y[b][m][t] = ep(bias[m] + sum_{c,j} W[c][m][j] * x[b][c][(t + pad - j*dil) / stride])
+ *                         over the (c, j) whose index is an integer; output_padding = 0
+ * x is [B][Cin][T], y [B][M][Tout]; an index outside [0, T) reads as zero, so Tout is the caller's: the layer's
+ * bm_conv1d_out_len(...) in the forward pass, the layer's INPUT length when one form serves as the data gradient of
+ * the other (strided <-> transposed, same stride / dil / pad).  `wpacked` = bm_pack_weights with rows m (no tap flip in
+ * either role); y_pre / y_out / ep_scale / ep_shift / act as bm_conv1d_nn; stats = [bm_conv_strided_stats_tiles][M][2]
+ * partial (sum, sumsq) of y_pre for bm_bn_finalize.  Shapes whose staged window does not fit (stride * (128 + tap
+ * span) > 576 floats in the strided form) return BM_ERR_UNSUPPORTED. */
+int bm_conv1d_out_len(int T, int KS, int stride, int dil, int pad, int transposed);
+int bm_conv_strided_stats_tiles(int B, int Tout, int stride, int transposed);
+int bm_conv1d_strided(const float* x, long x_bstride, const float* wpacked, const float* bias,
+                      const float* ep_scale, const float* ep_shift, float* y_pre, float* y_out, long y_bstride,
+                      float* stats, int B, int Cin, int M, int T, int Tout, int KS, int stride, int dil, int pad,
+                      int act, float leak, void* stream);
+int bm_conv1d_transposed(const float* x, long x_bstride, const float* wpacked, const float* bias,
+                         const float* ep_scale, const float* ep_shift, float* y_pre, float* y_out, long y_bstride,
+                         float* stats, int B, int Cin, int M, int T, int Tout, int KS, int stride, int dil, int pad,
+                         int act, float leak, void* stream);
+/* Weight gradient of both layers (autograd of bm/models/common.py:96, 112-114), one kernel, operand roles swapped:
+ *   part[split][r][q*KS + j] = sum over the split's share of (s, u) of a[s][r][u] * xl[s][q][u*stride + j*dil - pad]
+ * strided layer: a = dY [S][M][Tout], xl = x [S][Cin][T] -> dW[m][c][j]; transposed layer: a = x [S][Cin][T],
+ * xl = dY [S][M][Tout] -> dW[c][m][j].  Rows of a are U apart, rows of xl L apart.  Separate partial tiles, folded in
+ * a fixed order by bm_reduce_splits(part, out, 1, nsplit, R, Q, KS, ...): deterministic. */
+int bm_conv1d_strided_wgrad_suggest_splits(int R, int Q, int KS, int S, int U);
+int bm_conv1d_strided_wgrad(const float* a, long a_sstride, const float* xl, long xl_sstride, float* part, int S,
+                            int R, int Q, int U, int L, int KS, int stride, int dil, int pad, int nsplit,
+                            void* stream);
+
 /* ---- fp32-ACCURATE contraction on the bf16 matrix cores: exact 3-way bf16 split of both operands,
  * six partial products per MFMA block, fp32 accumulate (conv_nn_x3.hip / gemm_nt_x3.hip).  Same
  * contracts as bm_conv1d_nn / bm_gemm_nt; compute mode "f32x3". */
