@@ -612,3 +612,103 @@ class MaskedRegressionFn(torch.autograd.Function):
         dest, dout = H.regress_loss_bwd(estimate, output, mask, ctx.kind, _c(dloss), count,
                                         want_dout=ctx.needs_input_grad[1])
         return (dest if ctx.needs_input_grad[0] else None), dout, None, None, None
+
+
+def _lstm_layer_params(params, layer: int, dirs: int):
+    """[(w_ih, w_hh, b_ih, b_hh)] per direction out of nn.LSTM's flat parameter order."""
+    base = layer * dirs * 4
+    return [tuple(params[base + 4 * d:base + 4 * d + 4]) for d in range(dirs)]
+
+
+class LSTMFn(torch.autograd.Function):
+    """A whole nn.LSTM stack (bm/models/convrnn.py:25-35): ``num_layers`` layers, optionally bidirectional, zero
+    initial state.  x [B, In, T] -> (y [B, H * dirs, T], h_n [layers * dirs, B, H], c_n the same); ``params`` is
+    nn.LSTM's flat list (weight_ih, weight_hh, bias_ih, bias_hh per layer and direction), read as it is.
+
+    Inside, activations are time-major [T][C][B] (two torch transposes at the entry and the exit), so a time step is a
+    segment of the library's layout.  Per layer: the input projection of all steps is one 1x1 conv, the recurrence is
+    csrc/lstm.hip (one launch per step, both directions in it); backward: the reverse recurrence writes the gate
+    gradients dG, then dX is a 1x1 conv, dW_ih and dW_hh (on views shifted by one step) are gemm_nt contractions and the
+    bias gradients a channel sum.  ``dropout`` acts between layers in training mode only (a GPU torch mask, saved for
+    the backward pass), never after the last layer."""
+
+    @staticmethod
+    def forward(ctx, x, hidden_size: int, num_layers: int, bidirectional: bool, dropout: float, training: bool,
+                *params):
+        dirs = 2 if bidirectional else 1
+        assert len(params) == num_layers * dirs * 4, "LSTMFn expects nn.LSTM's parameters with biases"
+        Hd = hidden_size
+        inp = _c(_c(x).permute(2, 1, 0))                                  # [T, In, B]
+        T, _, B = inp.shape
+        saved, masks, h_n, c_n = [], [], [], []
+        for layer in range(num_layers):
+            In = inp.shape[1]
+            per_dir = _lstm_layer_params(params, layer, dirs)
+            gx = []
+            for w_ih, w_hh, b_ih, b_hh in per_dir:
+                wp = H.pack_weights(_c(w_ih), 1, 4 * Hd, In, 1, 0, In, 1, 0, shape=(B, 1))
+                gx.append(H.conv_nn(inp, wp, 4 * Hd, 1, 1, bias=b_ih + b_hh)[1])
+            y, gates, c = H.lstm_layer_fwd([_c(p[1]) for p in per_dir], gx)
+            del gx
+            saved += [inp, y, gates, c]
+            for d in range(dirs):
+                last = 0 if d else T - 1
+                h_n.append(y[last, d * Hd:(d + 1) * Hd].t())
+                c_n.append(c[d, last].t())
+            mask = None
+            inp = y
+            if dropout > 0. and training and layer < num_layers - 1:
+                mask = torch.bernoulli(torch.full_like(y, 1. - dropout)) / (1. - dropout)
+                inp = y * mask
+            masks.append(mask)
+        ctx.save_for_backward(*params, *saved, *[m for m in masks if m is not None])
+        ctx.cfg = (Hd, num_layers, dirs, [m is not None for m in masks])
+        return _c(inp.permute(2, 1, 0)), torch.stack(h_n), torch.stack(c_n)
+
+    @staticmethod
+    def backward(ctx, dout, dhn, dcn):
+        Hd, num_layers, dirs, has_mask = ctx.cfg
+        tensors = ctx.saved_tensors
+        nparams = num_layers * dirs * 4
+        params, saved = tensors[:nparams], tensors[nparams:nparams + 4 * num_layers]
+        masks = list(tensors[nparams + 4 * num_layers:])
+        dy = _c(_c(dout).permute(2, 1, 0)).clone()                        # [T, H * dirs, B]; written below
+        T, _, B = dy.shape
+        grads = [None] * nparams
+        for layer in reversed(range(num_layers)):
+            inp, y, gates, c = saved[4 * layer:4 * layer + 4]
+            In = inp.shape[1]
+            per_dir = _lstm_layer_params(params, layer, dirs)
+            if has_mask[layer]:
+                dy = dy * masks.pop()
+            for d in range(dirs):
+                last = 0 if d else T - 1
+                dy[last, d * Hd:(d + 1) * Hd] += dhn[layer * dirs + d].t()
+            dc = _c(dcn[layer * dirs:(layer + 1) * dirs].transpose(1, 2)).clone()      # [dirs, H, B]
+            dg = H.lstm_layer_bwd([_c(p[1]) for p in per_dir], dy, gates, c, dc)
+            need_dx = layer > 0 or ctx.needs_input_grad[0]
+            dx = None
+            for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(per_dir):
+                base = (layer * dirs + d) * 4
+                dgd = dg[d]
+                if ctx.needs_input_grad[6 + base]:
+                    grads[base] = H.gemm_nt(dgd, inp, T, 4 * Hd, In, B).view(4 * Hd, In)
+                if ctx.needs_input_grad[6 + base + 1]:
+                    if T > 1:
+                        # dW_hh = sum_t dG_t h_{t-1}^T: the same contraction on views one step apart (h of the step
+                        # before lives in the layer output at this direction's channel offset)
+                        a, hprev = (dgd[:-1], y[1:]) if d else (dgd[1:], y[:-1])
+                        hprev = hprev.reshape(-1)[d * Hd * B:]
+                        grads[base + 1] = H.gemm_nt(_c(a), hprev, T - 1, 4 * Hd, Hd, B,
+                                                    x_strides=(Hd * dirs * B, B)).view(4 * Hd, Hd)
+                    else:
+                        grads[base + 1] = torch.zeros_like(w_hh)
+                if ctx.needs_input_grad[6 + base + 2] or ctx.needs_input_grad[6 + base + 3]:
+                    db = H.channel_sum(dgd)
+                    grads[base + 2], grads[base + 3] = db, db.clone()
+                if need_dx:
+                    wpt = H.pack_weights(_c(w_ih), 1, In, 4 * Hd, 1, 0, 1, In, 0, shape=(B, 1))
+                    _, dx, _ = H.conv_nn(dgd, wpt, In, 1, 1, res=dx, out=dx)
+            dy = dx
+        dxo = _c(dy.permute(2, 1, 0)) if ctx.needs_input_grad[0] else None
+        return (dxo, None, None, None, None, None) + tuple(grads)

@@ -1135,3 +1135,68 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step: int, lr: float, beta1: flo
     check(lib().bm_adam_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), step,
                              lr, beta1, beta2, eps, grad_scale, _stream()), "bm_adam_step")
     weights_changed()
+
+
+# ------------------------------------------------------------------------------------------------
+# LSTM recurrence (csrc/lstm.hip): one call per (layer, pass) enqueues all T step launches, both directions of a
+# bidirectional layer in the same launches.  Exact-fp32 MFMA in every compute mode; time-major tensors [T][C][B].
+def _per_dir(ts, name, shape):
+    for t in ts:
+        _req(t, name)
+        assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+    return [_p(t) for t in ts] + [None] * (2 - len(ts))
+
+
+def lstm_layer_fwd(whh: tp.Sequence[torch.Tensor], gx: tp.Sequence[torch.Tensor]):
+    """whh[d] = weight_hh [4H, H] (the parameter itself), gx[d] [T, 4H, B] = W_ih x + b_ih + b_hh per direction ->
+    (y [T, H * dirs, B], gates [dirs, T, 4H, B] activated i, f, g, o, c [dirs, T, H, B]); zero initial state."""
+    dirs = len(whh)
+    assert dirs in (1, 2) and len(gx) == dirs
+    T, H4, B = gx[0].shape
+    Hd = H4 // 4
+    dev = gx[0].device
+    whh_p = _per_dir(whh, "lstm_layer_fwd.whh", (H4, Hd))
+    gx_p = _per_dir(gx, "lstm_layer_fwd.gx", (T, H4, B))
+    y = torch.empty(T, Hd * dirs, B, device=dev, dtype=torch.float32)
+    gates = torch.empty(dirs, T, H4, B, device=dev, dtype=torch.float32)
+    c = torch.empty(dirs, T, Hd, B, device=dev, dtype=torch.float32)
+    g_p = [_p(gates[d]) for d in range(dirs)] + [None] * (2 - dirs)
+    c_p = [_p(c[d]) for d in range(dirs)] + [None] * (2 - dirs)
+
+    def launch():
+        check(lib().bm_lstm_layer_fwd(*whh_p, *gx_p, _p(y), *g_p, *c_p, Hd, B, T, dirs, _stream()), "bm_lstm_layer_fwd")
+    if _timer is not None:
+        _timer.launch(f"lstm_step_fwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
+    else:
+        launch()
+    return y, gates, c
+
+
+def lstm_layer_bwd(whh: tp.Sequence[torch.Tensor], dy: torch.Tensor, gates: torch.Tensor, c: torch.Tensor,
+                   dc: torch.Tensor) -> torch.Tensor:
+    """dy [T, H * dirs, B] (dL/dh_n already added at each direction's last step), the saved gates / c of
+    ``lstm_layer_fwd``, dc [dirs, H, B] = dL/dc_n (OVERWRITTEN: the carried cell gradient) -> dg [dirs, T, 4H, B]."""
+    dirs = len(whh)
+    _req(dy, "lstm_layer_bwd.dy")
+    _req(gates, "lstm_layer_bwd.gates")
+    _req(c, "lstm_layer_bwd.c")
+    _req(dc, "lstm_layer_bwd.dc")
+    _, T, H4, B = gates.shape
+    Hd = H4 // 4
+    assert gates.shape[0] == dirs and tuple(dy.shape) == (T, Hd * dirs, B) and tuple(c.shape) == (dirs, T, Hd, B) \
+        and tuple(dc.shape) == (dirs, Hd, B), (dy.shape, gates.shape, c.shape, dc.shape)
+    whh_p = _per_dir(whh, "lstm_layer_bwd.whh", (H4, Hd))
+    dg = torch.empty_like(gates)
+    _touched(dc)
+
+    def two(t):
+        return [_p(t[d]) for d in range(dirs)] + [None] * (2 - dirs)
+
+    def launch():
+        check(lib().bm_lstm_layer_bwd(*whh_p, _p(dy), *two(gates), *two(c), *two(dg), *two(dc), Hd, B, T, dirs,
+                                      _stream()), "bm_lstm_layer_bwd")
+    if _timer is not None:
+        _timer.launch(f"lstm_step_bwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
+    else:
+        launch()
+    return dg

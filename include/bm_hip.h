@@ -93,6 +93,22 @@ int bm_conv1d_strided_wgrad(const float* a, long a_sstride, const float* xl, lon
                             int R, int Q, int U, int L, int KS, int stride, int dil, int pad, int nsplit,
                             void* stream);
 
+/* ---- LSTM recurrence, fp32 MFMA (lstm.hip)  bm/models/convrnn.py:25-35 (nn.LSTM inside ConvRNN) ----
+ * Time-major tensors [T][channels][B], B fastest.  One nn.LSTM layer per call, both directions when dirs = 2 (the *1
+ * pointers are ignored when dirs = 1); one kernel launch per time step, stream order is the only synchronisation.
+ *   forward   G_t = W_hh h_{t-1} + gx_t (gates i, f, g, o);  c_t = s(f) c_{t-1} + s(i) tanh(g);  h_t = s(o) tanh(c_t)
+ *             whh_d = weight_hh_l{k}[_reverse] [4H][H] as nn.LSTM keeps it; gx_d [T][4H][B] = W_ih x + b_ih + b_hh
+ *             (bm_conv1d_nn over all steps); y [T][H * dirs][B]; gates_d [T][4H][B] and c_d [T][H][B] are saved.
+ *   backward  dy = dL/dy with dL/dh_n added at each direction's last step; dc_d [H][B] = dL/dc_n on entry, overwritten;
+ *             dg_d [T][4H][B] = gradient of the gate pre-activations (operand of dX, dW_ih, dW_hh, the bias sums).
+ * Any H, B, T >= 1; initial state zero; deterministic (no atomics). */
+int bm_lstm_layer_fwd(const float* whh0, const float* whh1, const float* gx0, const float* gx1, float* y,
+                      float* gates0, float* gates1, float* c0, float* c1, int H, int B, int T, int dirs,
+                      void* stream);
+int bm_lstm_layer_bwd(const float* whh0, const float* whh1, const float* dy, const float* gates0,
+                      const float* gates1, const float* c0, const float* c1, float* dg0, float* dg1,
+                      float* dc0, float* dc1, int H, int B, int T, int dirs, void* stream);
+
 /* ---- fp32-ACCURATE contraction on the bf16 matrix cores: exact 3-way bf16 split of both operands,
  * six partial products per MFMA block, fp32 accumulate (conv_nn_x3.hip / gemm_nt_x3.hip).  Same
  * contracts as bm_conv1d_nn / bm_gemm_nt; compute mode "f32x3". */
