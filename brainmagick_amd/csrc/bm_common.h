@@ -49,6 +49,8 @@ __host__ __device__ __forceinline__ unsigned bm_div(unsigned n, const BmFastDiv&
 #endif
     return f.shift == 0 ? n : (t + ((n - t) >> 1)) >> (f.shift - 1);
 }
+// floor(a / b) for b > 0 (C's division truncates towards zero).
+__host__ __device__ __forceinline__ int bm_floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // Channel chunk of the packed-weight layout (see pack.hip / conv_nn.hip).
 #define BM_BKC 16

@@ -19,6 +19,22 @@ struct ConvNNArgs {
     int ntiles_n, ntiles_m;
 };
 
+// Staging of one (chunk, tap) A slab [BKC][BM] of the packed weights through registers into LDS, one float4 per
+// thread and pass I_ (exact-fp32 kernels: conv_nn.hip, conv_strided.hip).  Macros over NAMED float4 registers V_:
+// arrays (even with fully unrolled constant indices, or captured by lambdas) were left in scratch memory by hipcc's
+// SROA.  They expect `tid`, `a` (ConvNNArgs) and the constants BKC, Q (float4 per slab row), AREG (passes) in scope;
+// WSRC_ = the slab's first row, COL_ = the float4's first column as an expression in `q`, its index in the row.
+#define CONV_A_LOAD1(I_, V_, WSRC_, COL_)                                                         \
+    if (I_ < AREG) {                                                                              \
+        int e = tid + I_ * 256;                                                                   \
+        e = e < BKC * Q ? e : BKC * Q - 1;          /* clamp: unconditional load, guarded store */ \
+        const int r = e / Q, q = e - r * Q;                                                       \
+        V_ = *reinterpret_cast<const float4*>((WSRC_) + (long)r * a.Mpad + (COL_));               \
+    }
+#define CONV_A_STORE1(I_, V_, DST_)                                                               \
+    if (I_ < AREG && tid + I_ * 256 < BKC * Q)                                                    \
+        *reinterpret_cast<float4*>((DST_) + (tid + I_ * 256) * 4) = V_;
+
 // Per-row epilogue parameters of a tile (bias, affine scale, affine shift) staged once into LDS:
 // ep[0..BM) = bias, ep[BM..2BM) = scale, ep[2BM..3BM) = shift.  Reading them from global memory per
 // element serialises hundreds of dependent L2 round trips per wavefront at the end of every tile.
@@ -97,16 +113,19 @@ __device__ __forceinline__ void conv_ep_store_block(const ConvNNArgs& a, const f
 // wavefront w owns columns [32w, 32w+32)): bias, optional pre-activation store, optional per-tile
 // BatchNorm partial statistics, optional per-channel affine, activation, residual.
 // `tid` is the thread index inside the 4-wavefront group that owns the tile; `smem` is the workgroup's LDS,
-// free by now: [4 waves][BM][2] statistics scratch, then the 3 * BM staged row parameters.
+// free by now: [4 waves][BM][2] statistics scratch, then the 3 * BM staged row parameters.  Tile column n (n0 is the
+// tile's first) is output column n * cstride + c0: consecutive columns by default, one output phase of the strided
+// family (conv_strided.hip) otherwise.
 template <int MT>
 __device__ __forceinline__ void conv_tile_epilogue(const ConvNNArgs& a, f32x16 (&acc)[MT], float* smem,
-                                                   int b, int ntile, int m0, int n0, int tid) {
+                                                   int b, int ntile, int m0, int n0, int tid, int cstride = 1,
+                                                   int c0 = 0) {
     constexpr int BM = 32 * MT;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int nl = lane & 31;
     const int h = lane >> 5;
-    const int col = n0 + wave * 32 + nl;
+    const int col = (n0 + wave * 32 + nl) * cstride + c0;
     const bool col_ok = col < a.T;
     float* red = smem;
     float* ep = smem + 8 * BM;

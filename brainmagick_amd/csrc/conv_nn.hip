@@ -85,25 +85,15 @@ __global__ __launch_bounds__(256, 3) void conv_nn_kernel(ConvNNArgs a) {
 
 // NB: the staging registers are NAMED scalars handled by macros: arrays (even with fully unrolled
 // constant indices, or captured by lambdas) were left in scratch memory by hipcc's SROA.
-#define BM_A1(I_, V_)                                                                             \
-    if (I_ < AREG) {                                                                              \
-        int e = tid + I_ * 256;                                                                   \
-        e = e < BKC * Q ? e : BKC * Q - 1;          /* clamp: unconditional load, guarded store */ \
-        const int r = e / Q, q = e - r * Q;                                                       \
-        V_ = *reinterpret_cast<const float4*>(wsrc + (long)r * a.Mpad + q * 4);                   \
-    }
 #define BM_LOAD_A(S_)                                                                             \
     {                                                                                             \
         const float* wsrc = wg + (long)(S_) * BKC * a.Mpad;                                       \
-        BM_A1(0, a0) BM_A1(1, a1) BM_A1(2, a2)                                                    \
+        CONV_A_LOAD1(0, a0, wsrc, q * 4) CONV_A_LOAD1(1, a1, wsrc, q * 4) CONV_A_LOAD1(2, a2, wsrc, q * 4) \
     }
-#define BM_SA1(I_, V_)                                                                            \
-    if (I_ < AREG && tid + I_ * 256 < BKC * Q)                                                    \
-        *reinterpret_cast<float4*>(dst + (tid + I_ * 256) * 4) = V_;
 #define BM_STORE_A(BUF_)                                                                          \
     {                                                                                             \
         float* dst = As + (BUF_) * BKC * BM;                                                      \
-        BM_SA1(0, a0) BM_SA1(1, a1) BM_SA1(2, a2)                                                 \
+        CONV_A_STORE1(0, a0, dst) CONV_A_STORE1(1, a1, dst) CONV_A_STORE1(2, a2, dst)             \
     }
 #define BM_X1(RR_, K_, V_)                                                                        \
     {                                                                                             \
@@ -181,8 +171,6 @@ __global__ __launch_bounds__(256, 3) void conv_nn_kernel(ConvNNArgs a) {
         }
     }
 #undef BM_LOAD_A
-#undef BM_A1
-#undef BM_SA1
 #undef BM_X1
 #undef BM_XV1
 #undef BM_SX1

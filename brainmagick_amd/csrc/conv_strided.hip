@@ -20,9 +20,11 @@
 // of ONE output phase, so every output element has exactly one owner (no atomics); a phase without taps is bias only.
 //
 // Tiling as conv_nn.hip: 4 wavefronts, [32*MT] x [128] tile, weights pre-packed by pack.hip as [chunk][tap][16][Mpad],
-// software pipeline through registers into double-buffered LDS, one barrier per (chunk, tap) stage; the epilogue is
-// conv_common.h's (bias, pre-activation output, affine, activation, per-tile BatchNorm sums in the [tiles][M][2]
-// layout that bm_bn_finalize reads).
+// software pipeline through registers into double-buffered LDS, one barrier per (chunk, tap) stage.  The A-slab staging
+// and the epilogue are conv_common.h's, shared with conv_nn.hip: conv_tile_epilogue (bias, pre-activation output,
+// affine, activation, per-tile BatchNorm sums in the [tiles][M][2] layout that bm_bn_finalize reads), called with the
+// tile's column mapping.  Above the kernels one pair of autograd functions serves both families
+// (functional.Conv1dFn / ConvBNActFn).
 #include "conv_common.h"
 #include "mfma_split.h"
 
@@ -37,9 +39,6 @@ struct ConvStridedArgs {
     int ntiles_v;          // column tiles per output phase
     BmFastDiv fsi;
 };
-
-static inline int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-__device__ __forceinline__ int bm_floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // XP = 64-lane passes per staged window row (window <= 64 * XP floats)
 template <int MT, int XP>
@@ -101,27 +100,17 @@ __global__ __launch_bounds__(256, 2) void conv_strided_kernel(ConvStridedArgs g)
     for (int k = 0; k < 4 * XP; ++k) xr[k] = 0.f;
     const int nstage = a.nchunk * nv;
 
-#define BS_A1(I_, V_)                                                                             \
-    if (I_ < AREG) {                                                                              \
-        int e = tid + I_ * 256;                                                                   \
-        e = e < BKC * Q ? e : BKC * Q - 1;          /* clamp: unconditional load, guarded store */ \
-        const int r = e / Q, q = e - r * Q;                                                       \
-        int col = m0 + q * 4;                                                                     \
-        col = col <= a.Mpad - 4 ? col : a.Mpad - 4; /* rows past Mpad feed discarded outputs */    \
-        V_ = *reinterpret_cast<const float4*>(wsrc + (long)r * a.Mpad + col);                     \
-    }
+    // column of a float4 inside the slab row: rows past Mpad feed discarded outputs
+#define BS_COL (m0 + q * 4 <= a.Mpad - 4 ? m0 + q * 4 : a.Mpad - 4)
 #define BS_LOAD_A(CHUNK_, J_)                                                                     \
     {                                                                                             \
         const float* wsrc = a.wp + ((long)(CHUNK_) * a.KS + (J_)) * BKC * a.Mpad;                 \
-        BS_A1(0, a0) BS_A1(1, a1)                                                                 \
+        CONV_A_LOAD1(0, a0, wsrc, BS_COL) CONV_A_LOAD1(1, a1, wsrc, BS_COL)                       \
     }
-#define BS_SA1(I_, V_)                                                                            \
-    if (I_ < AREG && tid + I_ * 256 < BKC * Q)                                                    \
-        *reinterpret_cast<float4*>(dst + (tid + I_ * 256) * 4) = V_;
-#define BS_PUT_A(BUF_)                                                                          \
+#define BS_PUT_A(BUF_)                                                                            \
     {                                                                                             \
         float* dst = As + (BUF_) * BKC * BM;                                                      \
-        BS_SA1(0, a0) BS_SA1(1, a1)                                                               \
+        CONV_A_STORE1(0, a0, dst) CONV_A_STORE1(1, a1, dst)                                       \
     }
 #define BS_LOAD_X(CHUNK_)                                                                         \
     {                                                                                             \
@@ -195,60 +184,14 @@ __global__ __launch_bounds__(256, 2) void conv_strided_kernel(ConvStridedArgs g)
             }
         }
     }
-#undef BS_A1
+#undef BS_COL
 #undef BS_LOAD_A
-#undef BS_SA1
 #undef BS_PUT_A
 #undef BS_LOAD_X
 #undef BS_PUT_X
 
-    // ---- epilogue: conv_tile_epilogue with the tile's columns mapped to t = v * so + p ----
-    const int col = (v0 + wave * 32 + nl) * g.so + p;
-    const bool col_ok = col < a.T;
-    float* red = smem;                // [4 waves][BM][2] statistics scratch
-    float* ep = smem + 8 * BM;        // 3 * BM staged row parameters
-    __syncthreads();
-    conv_ep_stage_params(a, ep, BM, m0, tid, 256, b);
-    __syncthreads();
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        float v[16];
-        conv_ep_store_block(a, acc[mt], ep, BM, b, m0, mt * 32 + 4 * h, col, v);
-        if (a.stats) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                float s = (col_ok && m0 + rl < a.M) ? v[r] : 0.f;
-                float s2 = s * s;
-#pragma unroll
-                for (int o = 16; o > 0; o >>= 1) {
-                    s += __shfl_xor(s, o);
-                    s2 += __shfl_xor(s2, o);
-                }
-                if (nl == 0) {
-                    red[(wave * BM + rl) * 2 + 0] = s;
-                    red[(wave * BM + rl) * 2 + 1] = s2;
-                }
-            }
-        }
-    }
-    if (a.stats) {
-        __syncthreads();
-        for (int rl = tid; rl < BM; rl += 256) {
-            const int row = m0 + rl;
-            if (row < a.M) {
-                float s = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    s += red[(w * BM + rl) * 2 + 0];
-                    s2 += red[(w * BM + rl) * 2 + 1];
-                }
-                float* dst = a.stats + ((long)(b * a.ntiles_n + ntile) * a.M + row) * 2;
-                dst[0] = s;
-                dst[1] = s2;
-            }
-        }
-    }
+    // the tile's columns are those of ONE output phase: t = v * so + p
+    conv_tile_epilogue<MT>(a, acc, smem, b, ntile, m0, v0, tid, g.so, p);
 }
 
 template <int MT, int XP>
@@ -323,12 +266,12 @@ static int conv_strided_common(int scatter, const float* x, long x_bstride, cons
     int qmax;
     if (scatter) {
         g.si = 1; g.so = stride;
-        g.qmin = floordiv(pad - (KS - 1) * dil, stride);
-        qmax = floordiv(stride - 1 + pad, stride);
+        g.qmin = bm_floordiv(pad - (KS - 1) * dil, stride);
+        qmax = bm_floordiv(stride - 1 + pad, stride);
     } else {
         g.si = stride; g.so = 1;
-        g.qmin = floordiv(-pad, stride);
-        qmax = floordiv((KS - 1) * dil - pad, stride);
+        g.qmin = bm_floordiv(-pad, stride);
+        qmax = bm_floordiv((KS - 1) * dil - pad, stride);
     }
     g.PW = 128 + qmax - g.qmin;
     g.ntiles_v = cdiv(cdiv(Tout, g.so), 128);
@@ -561,8 +504,8 @@ extern "C" int bm_conv1d_strided_wgrad(const float* a, long a_sstride, const flo
     g.nsplit = nsplit;
     const int tj = wgrad_tj_for(KS);
     g.tiles_r = cdiv(R, 64); g.tiles_q = cdiv(Q, 64); g.ngroups = cdiv(KS, tj);
-    g.qmin = floordiv(-pad, stride);
-    const int qmax = floordiv((KS - 1) * dil - pad, stride);
+    g.qmin = bm_floordiv(-pad, stride);
+    const int qmax = bm_floordiv((KS - 1) * dil - pad, stride);
     g.PW = WG_BKT + qmax - g.qmin;
     g.W = stride * g.PW;
     g.PX = g.W | 1;

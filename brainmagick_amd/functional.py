@@ -63,38 +63,95 @@ def _conv_weight_grads(dy, x, weight, KS, dil, transposed_weight):
     return H.gemm_nt(dy, x, B, M, Cin, T, KS, dil).view(weight.shape)
 
 
+def _layer_forward(x, weight, geom, res=None, **kw):
+    """The layer's forward kernel -> (pre, out, stats) as ``H.conv_nn``.  ``geom`` = (dil, transposed, stride, pad) and
+    ``pad`` names the kernel family, which the CALLER chooses: None = the "same"-padding family (csrc/conv_nn*.hip:
+    nn.Conv1d with stride 1 and an odd kernel, or ConvTranspose1d(k=1)), a number = the strided / transposed family
+    (csrc/conv_strided.hip: gather form for nn.Conv1d [M, Cin, KS], scatter form for nn.ConvTranspose1d [Cin, M, KS]).
+    ``want_stats`` always yields BatchNorm partials: in the epilogue where the kernel has them (the wide f16x2 conv, the
+    strided family), by a channel_stats streaming pass otherwise.  Only the "same"-padding family fuses ``res``."""
+    dil, transposed, stride, pad = geom
+    if pad is not None:
+        assert res is None, "the strided family has no fused residual"
+        KS = weight.shape[2]
+        M = weight.shape[1] if transposed else weight.shape[0]
+        Tout = H.conv_out_len(x.shape[2], KS, stride, dil, pad, transposed)
+        wp = H.pack_strided_rows_second(weight) if transposed else H.pack_strided_rows_first(weight)
+        return H.conv_strided(x, wp, M, Tout, KS, stride, dil, pad, transposed, **kw)
+    assert stride == 1
+    if transposed:
+        Cin, M, KS = weight.shape
+        assert KS == 1, "ConvTranspose1d is only supported with kernel 1 (simpleconv.py:189)"
+        wp = H.pack_weights(weight, 1, M, Cin, 1, 0, 1, M, 0, shape=(x.shape[2], dil))
+    else:
+        M, Cin, KS = weight.shape
+        wp = H.pack_conv_fwd(weight, (x.shape[2], dil))
+    if kw.get("want_stats") and getattr(wp, "_bm_mode", "") != "f16x2":
+        pre, out, _ = H.conv_nn(x, wp, M, KS, dil, res=res, **dict(kw, want_stats=False))
+        return pre, out, H.channel_stats(pre)
+    return H.conv_nn(x, wp, M, KS, dil, res=res, **kw)
+
+
+def _layer_backward(ctx, dy, x, weight, geom, res=None, publish_amax=True):
+    """(dx, dw) of the layer of ``_layer_forward``.  Strided family: the data gradient is the OTHER form at the
+    layer's input length, the weight gradient one kernel with the operand roles swapped.  ``res`` (added to dx) and
+    ``publish_amax`` belong to the "same"-padding family."""
+    dil, transposed, stride, pad = geom
+    KS = weight.shape[2]
+    Cin, T = x.shape[1], x.shape[2]
+    dw = None
+    if ctx.needs_input_grad[1]:
+        if pad is None:
+            dw = _conv_weight_grads(dy, x, weight, KS, dil, transposed)
+        else:
+            a, xl = (x, dy) if transposed else (dy, x)
+            dw = H.conv_strided_wgrad(a, xl, KS, stride, dil, pad, out=H.grad_destination(weight)).view(weight.shape)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        if pad is not None:
+            # rows of the data gradient = the layer's input channels: dim 0 of a transposed weight, dim 1 of a Conv1d
+            # one
+            wp = H.pack_strided_rows_first(weight) if transposed else H.pack_strided_rows_second(weight)
+            _, dx, _ = H.conv_strided(dy, wp, Cin, T, KS, stride, dil, pad, not transposed)
+        else:
+            if transposed:
+                M = weight.shape[1]
+                wp = H.pack_weights(weight, 1, Cin, M, 1, 0, M, 1, 0, shape=(T, dil))
+            else:
+                wp = H.pack_conv_dgrad(weight, (T, dil))
+            _, dx, _ = H.conv_nn(dy, wp, Cin, KS, dil, res=res, publish_amax=publish_amax)
+    return dx, dw
+
+
 class Conv1dFn(torch.autograd.Function):
-    """nn.Conv1d ("same" padding, stride 1) or ConvTranspose1d(k=1) + bias [+ activation].
+    """nn.Conv1d or nn.ConvTranspose1d (``transposed_weight``) + bias [+ activation].  By default the layer has "same"
+    padding and stride 1 (a ConvTranspose1d then has kernel 1); a ``pad`` puts it on the strided / transposed kernels,
+    with any stride / kernel / padding (``_layer_forward``).
 
     Replaces F.conv1d at bm/models/simpleconv.py:113-120 (initial_linear), :185-189 (final head)
-    and bm/models/common.py:113-114 for layers without BatchNorm."""
+    and bm/models/common.py:96, 112-114 for layers without BatchNorm."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, dil: int, act: int, leak: float, transposed_weight: bool):
+    def forward(ctx, x, weight, bias, dil: int, act: int, leak: float, transposed_weight: bool, stride: int = 1,
+                pad=None):
         x, weight = _c(x), _c(weight)
-        if transposed_weight:
-            Cin, M, KS = weight.shape
-            assert KS == 1, "ConvTranspose1d is only supported with kernel 1 (simpleconv.py:189)"
-            wp = H.pack_weights(weight, 1, M, Cin, 1, 0, 1, M, 0, shape=(x.shape[2], dil))
-        else:
-            M, Cin, KS = weight.shape
-            wp = H.pack_conv_fwd(weight, (x.shape[2], dil))
+        geom = (dil, transposed_weight, stride, pad)
         need_pre = act != H.ACT_NONE and (x.requires_grad or weight.requires_grad)
-        if need_pre:
+        if need_pre and pad is None:
             # training: the pre-activation is saved anyway; the activation as a streaming pass over it is cheaper
             # than the conv kernel's general epilogue (erf per accumulator element with the matrix cores idle)
-            pre, _, _ = H.conv_nn(x, wp, M, KS, dil, bias=bias, want_pre=True, want_out=False)
+            pre, _, _ = _layer_forward(x, weight, geom, bias=bias, want_pre=True, want_out=False)
             out = H.affine_act_res(pre, None, None, None, act, leak)
         else:
-            pre, out, _ = H.conv_nn(x, wp, M, KS, dil, bias=bias, act=act, leak=leak)
+            pre, out, _ = _layer_forward(x, weight, geom, bias=bias, act=act, leak=leak, want_pre=need_pre)
         ctx.save_for_backward(x, weight, pre)
-        ctx.cfg = (dil, act, leak, transposed_weight, KS, bias is not None)
+        ctx.cfg = (geom, act, leak, bias is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, weight, pre = ctx.saved_tensors
-        dil, act, leak, transposed_weight, KS, has_bias = ctx.cfg
+        geom, act, leak, has_bias = ctx.cfg
         dout = _c(dout)
         dbias = None
         if act != H.ACT_NONE:
@@ -104,167 +161,49 @@ class Conv1dFn(torch.autograd.Function):
             dy = dout
             if has_bias:
                 dbias = H.channel_sum(dy)
-        dw = _conv_weight_grads(dy, x, weight, KS, dil, transposed_weight) \
-            if ctx.needs_input_grad[1] else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if transposed_weight:
-                Cin, M, _ = weight.shape
-                wp = H.pack_weights(weight, 1, Cin, M, 1, 0, M, 1, 0, shape=(dy.shape[2], dil))
-            else:
-                M, Cin, _ = weight.shape
-                wp = H.pack_conv_dgrad(weight, (dy.shape[2], dil))
-            _, dx, _ = H.conv_nn(dy, wp, Cin, KS, dil)
-        return dx, dw, dbias, None, None, None, None
+        dx, dw = _layer_backward(ctx, dy, x, weight, geom)
+        return (dx, dw, dbias) + (None,) * 6
 
 
 class ConvBNActFn(torch.autograd.Function):
-    """One ConvSequence layer: Conv1d -> BatchNorm1d -> activation [-> + input] as fused HIP
-    kernels (bm/models/common.py:113-119 + :146-147).
+    """One ConvSequence layer: conv -> BatchNorm1d -> activation [-> + input] as fused HIP kernels
+    (bm/models/common.py:112-120 + :146-147); ``stride`` / ``pad`` / ``transposed`` as in ``Conv1dFn``.
 
-    train: conv_nn (the wide f16x2 kernel adds the per-tile sums / sums of squares in its epilogue; the other
-    kernels are followed by a channel_stats streaming pass) -> bn_finalize (also updates the running statistics
-    like torch) -> affine_act_res.  eval: ONE conv_nn launch with the affine,
-    activation and residual folded in its epilogue."""
+    train: the conv kernel writes the pre-activation and the per-tile sums / sums of squares (``_layer_forward``)
+    -> bn_finalize (also updates the running statistics like torch) -> affine_act_res.  eval: ONE conv launch with the
+    affine, activation and residual folded in its epilogue."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, num_batches,
                 training: bool, dil: int, act: int, leak: float, residual: bool, momentum: float,
-                eps: float):
+                eps: float, stride: int = 1, pad=None, transposed: bool = False):
         x, weight = _c(x), _c(weight)
-        M, Cin, KS = weight.shape
-        B, _, T = x.shape
-        wp = H.pack_conv_fwd(weight, (T, dil))
+        geom = (dil, transposed, stride, pad)
         res = x if residual else None
         needs_grad = x.requires_grad or weight.requires_grad
         if training:
-            if getattr(wp, "_bm_mode", "") == "f16x2":     # the wide f16x2 conv adds the partial sums in its epilogue
-                pre, _, stats = H.conv_nn(x, wp, M, KS, dil, bias=bias, want_pre=True,
-                                          want_out=False, want_stats=True)
-            else:
-                pre, _, _ = H.conv_nn(x, wp, M, KS, dil, bias=bias, want_pre=True, want_out=False)
-                stats = H.channel_stats(pre)
-            mean, invstd, scale, shift = H.bn_finalize(stats, B * T, gamma, beta, running_mean,
+            pre, _, stats = _layer_forward(x, weight, geom, bias=bias, want_pre=True, want_out=False, want_stats=True)
+            mean, invstd, scale, shift = H.bn_finalize(stats, pre.shape[0] * pre.shape[2], gamma, beta, running_mean,
                                                        running_var, num_batches, momentum, eps)
             out = H.affine_act_res(pre, scale, shift, res, act, leak)
         else:
             mean, invstd, scale, shift = H.bn_eval_affine(gamma, beta, running_mean, running_var, eps)
-            pre, out, _ = H.conv_nn(x, wp, M, KS, dil, bias=bias, scale=scale, shift=shift, res=res,
-                                    act=act, leak=leak, want_pre=needs_grad)
+            pre, out, _ = _layer_forward(x, weight, geom, res=res, bias=bias, scale=scale, shift=shift, act=act,
+                                         leak=leak, want_pre=needs_grad)
         ctx.save_for_backward(x, weight, pre, scale, shift, mean, invstd)
-        ctx.cfg = (training, dil, act, leak, residual, KS, bias is not None)
+        ctx.cfg = (geom, training, act, leak, residual, bias is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, weight, pre, scale, shift, mean, invstd = ctx.saved_tensors
-        training, dil, act, leak, residual, KS, has_bias = ctx.cfg
+        geom, training, act, leak, residual, has_bias = ctx.cfg
         dout = _c(dout)
-        M, Cin, _ = weight.shape
         dy, dgamma, dbeta, dbias = H.act_bn_bwd(dout, pre, scale, shift, mean, invstd, training, act,
                                                 leak, want_affine_grads=True, want_dbias=has_bias)
-        dw = _conv_weight_grads(dy, x, weight, KS, dil, False) if ctx.needs_input_grad[1] else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            # dx feeds the previous layer's elementwise backward kernel: nobody needs its maximum
-            _, dx, _ = H.conv_nn(dy, H.pack_conv_dgrad(weight, (dy.shape[2], dil)), Cin, KS, dil,
-                                 res=dout if residual else None, publish_amax=False)
-        return (dx, dw, dbias, dgamma, dbeta) + (None,) * 10
-
-
-def _strided_forward(x, weight, transposed, stride, dil, pad, **kw):
-    """The layer's forward kernel: gather form for nn.Conv1d [M, Cin, KS], scatter form for nn.ConvTranspose1d
-    [Cin, M, KS] (csrc/conv_strided.hip)."""
-    KS = weight.shape[2]
-    M = weight.shape[1] if transposed else weight.shape[0]
-    Tout = H.conv_out_len(x.shape[2], KS, stride, dil, pad, transposed)
-    wp = H.pack_strided_rows_second(weight) if transposed else H.pack_strided_rows_first(weight)
-    return H.conv_strided(x, wp, M, Tout, KS, stride, dil, pad, transposed, **kw)
-
-
-def _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad):
-    """(dx, dw) of a strided / transposed layer: the data gradient is the OTHER form at the layer's input length, the
-    weight gradient one kernel with the operand roles swapped."""
-    KS = weight.shape[2]
-    dw = None
-    if ctx.needs_input_grad[1]:
-        dst = H.grad_destination(weight)
-        a, xl = (x, dy) if transposed else (dy, x)
-        dw = H.conv_strided_wgrad(a, xl, KS, stride, dil, pad, out=dst)
-        dw = dw.view(weight.shape)
-    dx = None
-    if ctx.needs_input_grad[0]:
-        Cin, T = x.shape[1], x.shape[2]
-        # rows of the data gradient = the layer's input channels: dim 0 of a transposed weight, dim 1 of a Conv1d one
-        wp = H.pack_strided_rows_first(weight) if transposed else H.pack_strided_rows_second(weight)
-        _, dx, _ = H.conv_strided(dy, wp, Cin, T, KS, stride, dil, pad, not transposed)
-    return dx, dw
-
-
-class StridedConv1dFn(torch.autograd.Function):
-    """nn.Conv1d with any stride / kernel / padding, or nn.ConvTranspose1d (``transposed``), + bias [+ activation]
-    (bm/models/common.py:96, 112-114 for layers without BatchNorm)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride: int, dil: int, pad: int, act: int, leak: float, transposed: bool):
-        x, weight = _c(x), _c(weight)
-        need_pre = act != H.ACT_NONE and (x.requires_grad or weight.requires_grad)
-        pre, out, _ = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, act=act, leak=leak,
-                                       want_pre=need_pre)
-        ctx.save_for_backward(x, weight, pre)
-        ctx.cfg = (stride, dil, pad, act, leak, transposed, bias is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, weight, pre = ctx.saved_tensors
-        stride, dil, pad, act, leak, transposed, has_bias = ctx.cfg
-        dout = _c(dout)
-        dbias = None
-        if act != H.ACT_NONE:
-            dy, _, _, dbias = H.act_bn_bwd(dout, pre, None, None, None, None, False, act, leak, want_dbias=has_bias)
-        else:
-            dy = dout
-            if has_bias:
-                dbias = H.channel_sum(dy)
-        dx, dw = _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad)
-        return (dx, dw, dbias) + (None,) * 6
-
-
-class StridedConvBNActFn(torch.autograd.Function):
-    """The same layer followed by BatchNorm1d and the activation (bm/models/common.py:112-120).
-
-    train: the conv kernel writes the pre-activation and the per-tile sums / sums of squares -> bn_finalize (running
-    statistics updated like torch) -> affine_act_res.  eval: ONE launch with the affine and the activation in the
-    epilogue.  The BatchNorm kernels are ConvBNActFn's."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, num_batches, training: bool,
-                stride: int, dil: int, pad: int, act: int, leak: float, transposed: bool, momentum: float, eps: float):
-        x, weight = _c(x), _c(weight)
-        needs_grad = x.requires_grad or weight.requires_grad
-        if training:
-            pre, _, stats = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, want_pre=True,
-                                             want_out=False, want_stats=True)
-            mean, invstd, scale, shift = H.bn_finalize(stats, pre.shape[0] * pre.shape[2], gamma, beta, running_mean,
-                                                       running_var, num_batches, momentum, eps)
-            out = H.affine_act_res(pre, scale, shift, None, act, leak)
-        else:
-            mean, invstd, scale, shift = H.bn_eval_affine(gamma, beta, running_mean, running_var, eps)
-            pre, out, _ = _strided_forward(x, weight, transposed, stride, dil, pad, bias=bias, scale=scale, shift=shift,
-                                           act=act, leak=leak, want_pre=needs_grad)
-        ctx.save_for_backward(x, weight, pre, scale, shift, mean, invstd)
-        ctx.cfg = (training, stride, dil, pad, act, leak, transposed, bias is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, weight, pre, scale, shift, mean, invstd = ctx.saved_tensors
-        training, stride, dil, pad, act, leak, transposed, has_bias = ctx.cfg
-        dy, dgamma, dbeta, dbias = H.act_bn_bwd(_c(dout), pre, scale, shift, mean, invstd, training, act, leak,
-                                                want_affine_grads=True, want_dbias=has_bias)
-        dx, dw = _strided_backward(ctx, dy, x, weight, transposed, stride, dil, pad)
-        return (dx, dw, dbias, dgamma, dbeta) + (None,) * 12
+        # dx feeds the previous layer's elementwise backward kernel: nobody needs its maximum
+        dx, dw = _layer_backward(ctx, dy, x, weight, geom, res=dout if residual else None, publish_amax=False)
+        return (dx, dw, dbias, dgamma, dbeta) + (None,) * 13
 
 
 class GLUConvFn(torch.autograd.Function):

@@ -91,6 +91,14 @@ def set_kernel_timer(timer: tp.Optional[KernelTimer]):
     _timer = timer
 
 
+def _timed(label, flops: float, launch):
+    """Run ``launch()``, under the installed KernelTimer if there is one.  ``label`` is a string or -- so that nothing
+    is formatted when no timer listens -- a function that returns it."""
+    if _timer is None:
+        return launch()
+    return _timer.launch(label() if callable(label) else label, flops, launch)
+
+
 def _p(t: tp.Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
@@ -346,10 +354,17 @@ def pack_weights(src: torch.Tensor, G: int, M: int, Cin: int, KS: int, sg: int, 
                                        _p(_opt(alpha, "alpha")), _stream()), "bm_pack_weights_x3")
         dst._bm_mode = mode                      # tells conv_nn which kernel family packed it
         return dst
-    n = lib().bm_packed_weight_elems(G, M, Cin, KS)
-    dst = torch.empty(n, device=src.device, dtype=torch.float32)
-    check(lib().bm_pack_weights(_p(src), _p(dst), G, M, Cin, KS, sg, sm, sc, sj, int(flip),
-                                _p(_opt(alpha, "alpha")), _stream()), "bm_pack_weights")
+    return pack_weights_f32(src, M, Cin, KS, sm, sc, sj, G, sg, flip, alpha)
+
+
+def pack_weights_f32(src: torch.Tensor, M: int, Cin: int, KS: int, sm: int, sc: int, sj: int, G: int = 1, sg: int = 0,
+                     flip: bool = False, alpha: tp.Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fp32 packed layout [group][chunk][tap][16][Mpad] whatever the compute mode (rows m = src[g*sg + m*sm + c*sc +
+    j*sj]): what the exact-fp32 kernels read -- every conv in "f32" mode, the strided family in all modes."""
+    _req(src, "pack_weights_f32.src")
+    dst = torch.empty(lib().bm_packed_weight_elems(G, M, Cin, KS), device=src.device, dtype=torch.float32)
+    check(lib().bm_pack_weights(_p(src), _p(dst), G, M, Cin, KS, sg, sm, sc, sj, int(flip), _p(_opt(alpha, "alpha")),
+                                _stream()), "bm_pack_weights")
     return dst
 
 
@@ -363,6 +378,14 @@ def pack_conv_dgrad(weight: torch.Tensor, shape=None) -> torch.Tensor:
     """nn.Conv1d weight [M, Cin, KS] for the data gradient: roles of M/Cin swapped, taps flipped."""
     M, Cin, KS = weight.shape
     return pack_weights(weight, 1, Cin, M, KS, 0, KS, Cin * KS, 1, flip=True, shape=shape)
+
+
+def _conv_outputs(x: torch.Tensor, M: int, T: int, want_pre: bool, want_out: bool, stats_shape=None):
+    """(y_pre | None, y_out | None, stats | None) of a conv on x [B, Cin, .]: fp32 [B, M, T] outputs and, with a
+    ``stats_shape``, its BatchNorm partials."""
+    def new(shape, want=True):
+        return torch.empty(shape, device=x.device, dtype=torch.float32) if want and shape is not None else None
+    return new((x.shape[0], M, T), want_pre), new((x.shape[0], M, T), want_out), new(stats_shape)
 
 
 def conv_nn(x: torch.Tensor, wpacked: torch.Tensor, M: int, KS: int = 1, dil: int = 1,
@@ -379,21 +402,16 @@ def conv_nn(x: torch.Tensor, wpacked: torch.Tensor, M: int, KS: int = 1, dil: in
     mode = getattr(wpacked, "_bm_mode", "f32")      # set by pack_weights
     _req(wpacked, "conv_nn.w", {"f32": torch.float32, "f16x2": torch.uint8}.get(mode, torch.bfloat16))
     B, Cin, T = x.shape
-    y_pre = torch.empty(B, M, T, device=x.device, dtype=torch.float32) if want_pre else None
+    channel_major = want_stats and mode == "f16x2"     # a channel's partials are one contiguous run for bn_finalize
+    stats_shape = None if not want_stats else (M, lib().bm_conv_h2_stats_tiles(B, T), 2) if channel_major else \
+        (lib().bm_conv_stats_tiles(B, T), M, 2)
+    y_pre, y_out, stats = _conv_outputs(x, M, T, want_pre, want_out and out is None, stats_shape)
+    if channel_major:
+        stats._bm_channel_major = True
     if out is not None:
         _req(out, "conv_nn.out")
         assert want_out and out.numel() == B * M * T, (out.shape, (B, M, T))
-        y_out = out
-        _touched(y_out)
-    else:
-        y_out = torch.empty(B, M, T, device=x.device, dtype=torch.float32) if want_out else None
-    stats = None
-    if want_stats:
-        if mode == "f16x2":     # channel-major: a channel's partials are one contiguous run for bn_finalize
-            stats = torch.empty(M, lib().bm_conv_h2_stats_tiles(B, T), 2, device=x.device, dtype=torch.float32)
-            stats._bm_channel_major = True
-        else:
-            stats = torch.empty(lib().bm_conv_stats_tiles(B, T), M, 2, device=x.device, dtype=torch.float32)
+        y_out = _touched(out)
     if res is not None:
         _req(res, "conv_nn.res")
         assert res.shape == (B, M, T), (res.shape, (B, M, T))
@@ -412,14 +430,14 @@ def conv_nn(x: torch.Tensor, wpacked: torch.Tensor, M: int, KS: int = 1, dil: in
 
         def launch():
             check(fn(_p(x), Cin * T, _p(wpacked), *common, _stream()), f"bm_conv1d_nn[{mode}]")
-    if _timer is not None:
+
+    def label():
         if mode == "f16x2":
             tile = f"{KS},{lib().bm_conv_h2_mw_for(M)}"
         else:
             tile = (lib().bm_conv_mt_for if mode == "f32" else lib().bm_conv_x3_mt_for)(M)
-        _timer.launch(f"conv_nn{_MODE_SUFFIX[mode]}_kernel<{tile}>", 2.0 * B * T * M * Cin * KS, launch)
-    else:
-        launch()
+        return f"conv_nn{_MODE_SUFFIX[mode]}_kernel<{tile}>"
+    _timed(label, 2.0 * B * T * M * Cin * KS, launch)
     return y_pre, y_out, stats
 
 
@@ -437,14 +455,6 @@ def conv_out_len(T: int, KS: int, stride: int, dil: int, pad: int, transposed: b
         raise RuntimeError(f"Calculated padded input size per channel: ({T + 2 * pad}). Kernel size: "
                            f"({dil * (KS - 1) + 1}). Kernel size can't be greater than actual input size")
     return Tout
-
-
-def pack_weights_f32(src: torch.Tensor, M: int, Cin: int, KS: int, sm: int, sc: int, sj: int) -> torch.Tensor:
-    """The fp32 packed layout [chunk][tap][16][Mpad] whatever the compute mode (rows m = src[m*sm + c*sc + j*sj])."""
-    _req(src, "pack_weights_f32.src")
-    dst = torch.empty(lib().bm_packed_weight_elems(1, M, Cin, KS), device=src.device, dtype=torch.float32)
-    check(lib().bm_pack_weights(_p(src), _p(dst), 1, M, Cin, KS, 0, sm, sc, sj, 0, None, _stream()), "bm_pack_weights")
-    return dst
 
 
 def pack_strided_rows_first(weight: torch.Tensor) -> torch.Tensor:
@@ -470,12 +480,9 @@ def conv_strided(x: torch.Tensor, wpacked: torch.Tensor, M: int, Tout: int, KS: 
     B, Cin, T = x.shape
     if Tout < 1:
         raise RuntimeError(f"conv_strided: output length {Tout} < 1")
-    y_pre = torch.empty(B, M, Tout, device=x.device, dtype=torch.float32) if want_pre else None
-    y_out = torch.empty(B, M, Tout, device=x.device, dtype=torch.float32) if want_out else None
-    stats = None
-    if want_stats:
-        stats = torch.empty(lib().bm_conv_strided_stats_tiles(B, Tout, stride, int(transposed)), M, 2, device=x.device,
-                            dtype=torch.float32)
+    y_pre, y_out, stats = _conv_outputs(
+        x, M, Tout, want_pre, want_out,
+        (lib().bm_conv_strided_stats_tiles(B, Tout, stride, int(transposed)), M, 2) if want_stats else None)
     fn = lib().bm_conv1d_transposed if transposed else lib().bm_conv1d_strided
     name = "conv_transposed_kernel" if transposed else "conv_strided_kernel"
 
@@ -483,12 +490,8 @@ def conv_strided(x: torch.Tensor, wpacked: torch.Tensor, M: int, Tout: int, KS: 
         check(fn(_p(x), Cin * T, _p(wpacked), _p(_opt(bias, "bias")), _p(_opt(scale, "scale")), _p(_opt(shift, "shift")),
                  _p(y_pre), _p(y_out), M * Tout, _p(stats), B, Cin, M, T, Tout, KS, stride, dil, pad, act, leak,
                  _stream()), "bm_conv1d_transposed" if transposed else "bm_conv1d_strided")
-    if _timer is not None:
-        taps = KS if not transposed else -(-KS // stride)
-        _timer.launch(f"{name}<K={KS},s={stride}>", 2.0 * B * (Tout if not transposed else T * stride) * M * Cin * taps,
-                      launch)
-    else:
-        launch()
+    taps = KS if not transposed else -(-KS // stride)
+    _timed(f"{name}<K={KS},s={stride}>", 2.0 * B * (Tout if not transposed else T * stride) * M * Cin * taps, launch)
     return y_pre, y_out, stats
 
 
@@ -514,10 +517,7 @@ def conv_strided_wgrad(a: torch.Tensor, xl: torch.Tensor, KS: int, stride: int, 
     def launch():
         check(lib().bm_conv1d_strided_wgrad(_p(a), R * U, _p(xl), Q * L, _p(part), S, R, Q, U, L, KS, stride, dil, pad,
                                             nsplit, _stream()), "bm_conv1d_strided_wgrad")
-    if _timer is not None:
-        _timer.launch(f"conv_strided_wgrad_kernel<K={KS},s={stride}>", 2.0 * S * U * R * Q * KS, launch)
-    else:
-        launch()
+    _timed(f"conv_strided_wgrad_kernel<K={KS},s={stride}>", 2.0 * S * U * R * Q * KS, launch)
     if part is not out:
         check(lib().bm_reduce_splits(_p(part), _p(out), 1, nsplit, R, Q, KS, R * Q * KS, Q * KS, KS, 1, _stream()),
               "bm_reduce_splits")
@@ -649,10 +649,7 @@ def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, K
             check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1],
                      _p(_opt(order, "order", torch.int32)), _p(_opt(seg, "seg", torch.int32)), _p(part), S,
                      G, M, Cn, T, KS, dil, nsplit, _stream()), "bm_gemm_nt")
-    if _timer is not None:
-        _timer.launch(f"gemm_nt{_MODE_SUFFIX[mode]}_kernel<KS={KS}>", 2.0 * S * T * M * Cn * KS, launch)
-    else:
-        launch()
+    _timed(f"gemm_nt{_MODE_SUFFIX[mode]}_kernel<KS={KS}>", 2.0 * S * T * M * Cn * KS, launch)
     if part is not out:
         check(lib().bm_reduce_splits(_p(part), _p(out), G, nsplit, M, Cn, KS, *out_strides,
                                      _stream()), "bm_reduce_splits")
@@ -733,10 +730,7 @@ def gemm_nt_partials(a, x, S, M, Cn, T, a_strides, x_strides, nsplit=None):
         def launch():
             check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1], None, None, _p(part),
                      S, 1, M, Cn, T, 1, 1, nsplit, _stream()), "bm_gemm_nt")
-    if _timer is not None:
-        _timer.launch("clip_scores:gemm_nt" + _MODE_SUFFIX[mode], 2.0 * S * T * M * Cn, launch)
-    else:
-        launch()
+    _timed("clip_scores:gemm_nt" + _MODE_SUFFIX[mode], 2.0 * S * T * M * Cn, launch)
     return part
 
 
@@ -1140,10 +1134,13 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step: int, lr: float, beta1: flo
 # ------------------------------------------------------------------------------------------------
 # LSTM recurrence (csrc/lstm.hip): one call per (layer, pass) enqueues all T step launches, both directions of a
 # bidirectional layer in the same launches.  Exact-fp32 MFMA in every compute mode; time-major tensors [T][C][B].
-def _per_dir(ts, name, shape):
-    for t in ts:
-        _req(t, name)
-        assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+def _per_dir(ts, name=None, shape=None):
+    """The two pointer arguments of a per-direction operand (None for the direction a one-directional layer lacks);
+    ``ts`` = a list of tensors or one tensor [dirs, ...].  With a ``name`` every entry is checked against ``shape``."""
+    if name is not None:
+        for t in ts:
+            _req(t, name)
+            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
     return [_p(t) for t in ts] + [None] * (2 - len(ts))
 
 
@@ -1160,15 +1157,11 @@ def lstm_layer_fwd(whh: tp.Sequence[torch.Tensor], gx: tp.Sequence[torch.Tensor]
     y = torch.empty(T, Hd * dirs, B, device=dev, dtype=torch.float32)
     gates = torch.empty(dirs, T, H4, B, device=dev, dtype=torch.float32)
     c = torch.empty(dirs, T, Hd, B, device=dev, dtype=torch.float32)
-    g_p = [_p(gates[d]) for d in range(dirs)] + [None] * (2 - dirs)
-    c_p = [_p(c[d]) for d in range(dirs)] + [None] * (2 - dirs)
 
     def launch():
-        check(lib().bm_lstm_layer_fwd(*whh_p, *gx_p, _p(y), *g_p, *c_p, Hd, B, T, dirs, _stream()), "bm_lstm_layer_fwd")
-    if _timer is not None:
-        _timer.launch(f"lstm_step_fwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
-    else:
-        launch()
+        check(lib().bm_lstm_layer_fwd(*whh_p, *gx_p, _p(y), *_per_dir(gates), *_per_dir(c), Hd, B, T, dirs, _stream()),
+              "bm_lstm_layer_fwd")
+    _timed(f"lstm_step_fwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
     return y, gates, c
 
 
@@ -1189,14 +1182,8 @@ def lstm_layer_bwd(whh: tp.Sequence[torch.Tensor], dy: torch.Tensor, gates: torc
     dg = torch.empty_like(gates)
     _touched(dc)
 
-    def two(t):
-        return [_p(t[d]) for d in range(dirs)] + [None] * (2 - dirs)
-
     def launch():
-        check(lib().bm_lstm_layer_bwd(*whh_p, _p(dy), *two(gates), *two(c), *two(dg), *two(dc), Hd, B, T, dirs,
-                                      _stream()), "bm_lstm_layer_bwd")
-    if _timer is not None:
-        _timer.launch(f"lstm_step_bwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
-    else:
-        launch()
+        check(lib().bm_lstm_layer_bwd(*whh_p, _p(dy), *_per_dir(gates), *_per_dir(c), *_per_dir(dg), *_per_dir(dc),
+                                      Hd, B, T, dirs, _stream()), "bm_lstm_layer_bwd")
+    _timed(f"lstm_step_bwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
     return dg

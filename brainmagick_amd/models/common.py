@@ -116,8 +116,9 @@ class ConvSequence(nn.Module):
     A layer with ``stride == 1``, an odd kernel and ``decode=False`` (every layer SimpleConv builds) runs on the
     "same"-padding kernels above.  Every other layer -- the reference's own defaults ``kernel=4, stride=2``, and
     ``decode=True``, which builds ``nn.ConvTranspose1d`` modules like the reference (ConvRNN's decoder) -- runs on the
-    strided / transposed kernels (``BF.StridedConv1dFn`` / ``BF.StridedConvBNActFn``, csrc/conv_strided.hip); there
-    the skip addition follows the reference's rule ``x.shape == old_x.shape`` (common.py:146)."""
+    strided / transposed kernels (the same ``BF.Conv1dFn`` / ``BF.ConvBNActFn``, given a stride and a padding:
+    csrc/conv_strided.hip); there the skip addition follows the reference's rule ``x.shape == old_x.shape``
+    (common.py:146)."""
 
     def __init__(self, channels: tp.Sequence[int], kernel: int = 4, dilation_growth: int = 1,
                  dilation_period: tp.Optional[int] = None, stride: int = 2,
@@ -188,41 +189,21 @@ class ConvSequence(nn.Module):
                 self.glus.append(None)
             self._plan.append(plan)
 
-    def _grouped_layer(self, x, plan, code, leak, fused_residual):
-        """``groups`` > 1 (off the hot path: no grid of the paper sets it): conv, BatchNorm and activation are all
+    def _conv_layer(self, x, plan, code, leak, fused_residual):
+        """conv [-> BatchNorm] -> activation of one layer, on the kernel family that ``plan["strided"]`` names.
+
+        ``groups`` > 1 (off the hot path: no grid of the paper sets it): conv, BatchNorm and activation are all
         per-channel or block-diagonal, so the layer is `groups` independent layers on channel slices -- the same fused
-        functions on views of the parameters and buffers (``num_batches_tracked`` counts once)."""
+        functions on views of the parameters and buffers (``num_batches_tracked`` counts once).  nn.ConvTranspose1d
+        keeps its weight as [in, out / groups, K], so a group is a slice of INPUT channels there and of output channels
+        in nn.Conv1d.  With one group nothing is sliced, copied or concatenated."""
         conv, bn = plan["conv"], plan["bn"]
+        stride, pad, decode = plan["strided"] or (1, None, False)       # pad None = the "same"-padding family
         G = conv.groups
         cin, cout = conv.in_channels // G, conv.out_channels // G
         outs = []
         # snapshot of the counter BEFORE group 0 increments it: with momentum=None (cumulative average) every group
         # must see the same count
-        count0 = bn.num_batches_tracked.clone() if bn is not None and G > 1 else None
-        for g in range(G):
-            xg = x[:, g * cin:(g + 1) * cin].contiguous()
-            w = conv.weight[g * cout:(g + 1) * cout]
-            b = conv.bias[g * cout:(g + 1) * cout] if conv.bias is not None else None
-            if bn is not None:
-                sl = slice(g * cout, (g + 1) * cout)
-                count = bn.num_batches_tracked if g == G - 1 else count0.clone()   # the module's counter moves once, last
-                outs.append(BF.ConvBNActFn.apply(
-                    xg, w, b, bn.weight[sl], bn.bias[sl], bn.running_mean[sl], bn.running_var[sl], count,
-                    self.training, plan["dilation"], code, leak, fused_residual, bn.momentum, bn.eps))
-            else:
-                outs.append(BF.Conv1dFn.apply(xg, w, b, plan["dilation"], code, leak, False))
-        return torch.cat(outs, dim=1)
-
-    def _strided_layer(self, x, plan, code, leak):
-        """A layer with a stride, an even kernel or ``decode`` (nn.ConvTranspose1d): conv [-> BatchNorm] -> activation
-        on the strided / transposed kernels.  ``groups`` > 1 as in ``_grouped_layer``: independent layers on channel
-        slices; nn.ConvTranspose1d keeps its weight as [in, out / groups, K], so a group is a slice of INPUT channels
-        there and of output channels in nn.Conv1d."""
-        conv, bn = plan["conv"], plan["bn"]
-        stride, pad, decode = plan["strided"]
-        G = conv.groups
-        cin, cout = conv.in_channels // G, conv.out_channels // G
-        outs = []
         count0 = bn.num_batches_tracked.clone() if bn is not None and G > 1 else None
         for g in range(G):
             if G == 1:
@@ -236,11 +217,11 @@ class ConvSequence(nn.Module):
                 bnp = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if sl is None else \
                     (bn.weight[sl], bn.bias[sl], bn.running_mean[sl], bn.running_var[sl])
                 count = bn.num_batches_tracked if g == G - 1 else count0.clone()   # the module's counter moves once, last
-                outs.append(BF.StridedConvBNActFn.apply(
-                    xg, w, b, *bnp, count, self.training, stride, plan["dilation"], pad, code, leak, decode,
-                    bn.momentum, bn.eps))
+                outs.append(BF.ConvBNActFn.apply(
+                    xg, w, b, *bnp, count, self.training, plan["dilation"], code, leak, fused_residual, bn.momentum,
+                    bn.eps, stride, pad, decode))
             else:
-                outs.append(BF.StridedConv1dFn.apply(xg, w, b, stride, plan["dilation"], pad, code, leak, decode))
+                outs.append(BF.Conv1dFn.apply(xg, w, b, plan["dilation"], code, leak, decode, stride, pad))
         return outs[0] if G == 1 else torch.cat(outs, dim=1)
 
     def forward(self, x: tp.Any) -> tp.Any:
@@ -254,22 +235,11 @@ class ConvSequence(nn.Module):
             old_x = x
             if plan["pre"] is not None:
                 x = plan["pre"](x)                                  # nn.Dropout on the input of the sequence
-            fused_residual = residual and not plan["post"] and plan["pre"] is None
-            if plan["strided"] is not None:
-                x = self._strided_layer(x, plan, code, leak)
-                # the addition is decided below, once the extras have run, by the reference's shape rule
-                # (common.py:146): with a stride or an even kernel equal channel counts do not mean equal lengths
-                fused_residual = False
-            elif conv.groups != 1:
-                x = self._grouped_layer(x, plan, code, leak, fused_residual)
-            elif plan["bn"] is not None:
-                bn = plan["bn"]
-                x = BF.ConvBNActFn.apply(
-                    x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                    bn.num_batches_tracked, self.training, plan["dilation"], code, leak, fused_residual,
-                    bn.momentum, bn.eps)
-            else:
-                x = BF.Conv1dFn.apply(x, conv.weight, conv.bias, plan["dilation"], code, leak, False)
+            # the strided family never fuses: its addition is decided below, once the extras have run, by the
+            # reference's shape rule (common.py:146) -- with a stride or an even kernel equal channel counts do not mean
+            # equal lengths
+            fused_residual = residual and not plan["post"] and plan["pre"] is None and plan["strided"] is None
+            x = self._conv_layer(x, plan, code, leak, fused_residual)
             for op in plan["post"]:                                 # the off-path extras, in the reference's order
                 if op[0] == "dropout":
                     x = op[1](x)

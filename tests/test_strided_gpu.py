@@ -246,7 +246,7 @@ def test_too_short_input_raises_before_any_launch(H):
     H.set_kernel_timer(timer)
     try:
         with pytest.raises(RuntimeError, match="Kernel size can't be greater than actual input size"):
-            BF.StridedConv1dFn.apply(x.cuda(), w.cuda(), None, 2, 1, 0, H.ACT_NONE, 0., False)
+            BF.Conv1dFn.apply(x.cuda(), w.cuda(), None, 1, H.ACT_NONE, 0., False, 2, 0)      # stride 2, padding 0
         torch.manual_seed(0)
         decoder = ConvSequence((4, 6), kernel=4, stride=2, decode=True).cuda()
         with pytest.raises(RuntimeError, match="Output size is too small"):
