@@ -22,6 +22,15 @@ template <> struct Pack<4> {
     __device__ void st(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 };
 
+// host: launch `kernel<4>` (16-byte accesses) where `vec4` holds, `kernel<1>` (dwords) otherwise, with the same arguments
+#define LAUNCH_VEC(vec4, kernel, grid, stream, ...)                                              \
+    do {                                                                                         \
+        if (vec4) hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, stream, __VA_ARGS__);        \
+        else hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);             \
+    } while (0)
+// host: workgroups of 256 threads of a flat grid-stride kernel over n items
+static int flat_blocks(long n) { return (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256); }
+
 // Walk of the flat (segment, vector) index e = threadIdx.x, threadIdx.x + blockDim.x, ... of a workgroup's
 // [nb segments][TV vectors] slab without a division per element (the (channel, split) kernels below spend a
 // dozen iterations per thread; `e / TV` per iteration was a fifth of their instructions).
@@ -36,6 +45,50 @@ struct SlabWalk {
         if (tv >= TV) { tv -= TV; ++bl; }
     }
 };
+
+// The slab of one (channel, split) workgroup: segments [b0, b0 + nb) of the batch, near-equal over the splits, each row
+// of it TV vectors of VEC floats.
+struct Slab {
+    int b0, nb, TV;
+    __device__ Slab(int B, int split, int nsplit, int T, int VEC)
+        : b0((int)((long)B * split / nsplit)), nb((int)((long)B * (split + 1) / nsplit) - b0), TV(T / VEC) {}
+};
+
+#ifndef BWD_UNROLL
+#define BWD_UNROLL 4      // slab positions per loop trip of the backward kernels
+#endif
+
+// Walks a workgroup's slab in trips of BWD_UNROLL positions per thread:
+//     SLAB_TRIPS_BEGIN(sl, AT, Data, LOAD)  <statements that consume position q: off[q], data[q]>  SLAB_TRIPS_END
+// `AT(bl, tv)` is an expression for the element offset of vector tv of the slab's segment bl, and `LOAD(d, o, o2)` the
+// statements that issue the loads at that offset into `d`, of type Data.  SLAB_TRIPS_BEGIN2 takes a second offset
+// expression for a kernel that reads two tensors of different shapes (off2[q]).  All loads of a trip are issued before
+// the first use: two 16-byte loads in flight per thread left these (channel, split) kernels latency-bound at ~5.0 TB/s
+// (the flat-grid forward kernels reach 5.8-6.0).  The loads are unconditional -- a position past the slab re-reads the
+// trip's first one and is not consumed -- so that nothing but the address arithmetic sits between them.
+// (A macro pair, not a function template taking lambdas: that form changed the instruction schedule and the register
+// counts of bn_bwd_reduce / bn_bwd_apply, this one leaves them byte-identical -- profiles/norm_act_one_slab_isa.txt.)
+#define SLAB_TRIPS_BEGIN2(sl, AT, AT2, Data, LOAD)                              \
+    SlabWalk w((sl).TV, threadIdx.x, blockDim.x);                               \
+    while (w.bl < (sl).nb) {                                                    \
+        long off[BWD_UNROLL];                                                   \
+        bool ok[BWD_UNROLL];                                                    \
+        long off2[BWD_UNROLL];                                                  \
+        Data data[BWD_UNROLL];                                                  \
+        _Pragma("unroll") for (int q = 0; q < BWD_UNROLL; ++q) {                \
+            ok[q] = w.bl < (sl).nb;                                             \
+            off[q] = ok[q] ? AT(w.bl, w.tv) : off[0];                           \
+            off2[q] = ok[q] ? AT2(w.bl, w.tv) : off2[0];                        \
+            LOAD(data[q], off[q], off2[q]);                                     \
+            if (ok[q]) w.next();                                                \
+        }                                                                       \
+        _Pragma("unroll") for (int q = 0; q < BWD_UNROLL; ++q) {                \
+            if (!ok[q]) continue;
+#define SLAB_NO_OFF2(bl, tv) 0L
+#define SLAB_TRIPS_BEGIN(sl, AT, Data, LOAD) SLAB_TRIPS_BEGIN2(sl, AT, SLAB_NO_OFF2, Data, LOAD)
+#define SLAB_TRIPS_END \
+        }              \
+    }
 
 // Block reduction of NV doubles (sum); result valid in thread 0.
 template <int NV>
@@ -99,16 +152,26 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, long tstride
     }
 }
 
+// both layouts of the partials: (tstride, cstride) are the strides of the tile and the channel index
+static int bn_finalize(const char* what, const float* stats, long tstride, long cstride, int ntiles, int C, long count,
+                       const float* gamma, const float* beta, float* running_mean, float* running_var,
+                       long* num_batches, float momentum, float eps, float* mean, float* invstd, float* scale,
+                       float* shift, void* stream) {
+    BM_REQUIRE(stats && mean && invstd && scale && shift, "%s: null pointer", what);
+    BM_REQUIRE(C > 0 && ntiles > 0 && count > 0, "%s: bad dims", what);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, stats, tstride, cstride, ntiles, C,
+                       (double)count, gamma, beta, running_mean, running_var, num_batches, momentum,
+                       eps, mean, invstd, scale, shift);
+    return bm_check_launch(what);
+}
+
+// tile-major partials stats[ntiles][C][2]
 extern "C" int bm_bn_finalize(const float* stats, int ntiles, int C, long count, const float* gamma,
                               const float* beta, float* running_mean, float* running_var,
                               long* num_batches, float momentum, float eps, float* mean,
                               float* invstd, float* scale, float* shift, void* stream) {
-    BM_REQUIRE(stats && mean && invstd && scale && shift, "bn_finalize: null pointer");
-    BM_REQUIRE(C > 0 && ntiles > 0 && count > 0, "bn_finalize: bad dims");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, stats, (long)C * 2, 2L, ntiles, C,
-                       (double)count, gamma, beta, running_mean, running_var, num_batches, momentum,
-                       eps, mean, invstd, scale, shift);
-    return bm_check_launch("bn_finalize");
+    return bn_finalize("bn_finalize", stats, (long)C * 2, 2L, ntiles, C, count, gamma, beta, running_mean, running_var,
+                       num_batches, momentum, eps, mean, invstd, scale, shift, stream);
 }
 
 // The same for channel-major partials stats[C][ntiles][2] (what the wide f16x2 conv writes from its epilogue: a
@@ -117,12 +180,8 @@ extern "C" int bm_bn_finalize_cm(const float* stats, int ntiles, int C, long cou
                                  const float* beta, float* running_mean, float* running_var,
                                  long* num_batches, float momentum, float eps, float* mean,
                                  float* invstd, float* scale, float* shift, void* stream) {
-    BM_REQUIRE(stats && mean && invstd && scale && shift, "bn_finalize_cm: null pointer");
-    BM_REQUIRE(C > 0 && ntiles > 0 && count > 0, "bn_finalize_cm: bad dims");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, stats, 2L, (long)ntiles * 2, ntiles, C,
-                       (double)count, gamma, beta, running_mean, running_var, num_batches, momentum,
-                       eps, mean, invstd, scale, shift);
-    return bm_check_launch("bn_finalize_cm");
+    return bn_finalize("bn_finalize_cm", stats, 2L, (long)ntiles * 2, ntiles, C, count, gamma, beta, running_mean,
+                       running_var, num_batches, momentum, eps, mean, invstd, scale, shift, stream);
 }
 
 // eval mode: scale/shift from the running statistics.
@@ -190,19 +249,11 @@ extern "C" int bm_affine_act_res(const float* y, const float* scale, const float
     BM_REQUIRE(n < 0xffffffffL, "affine_act_res: tensor of %ld elements (32-bit element index)", n);
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    int nblk = 0;
-    if (T % 4 == 0) {
-        const long nvec = n / 4;
-        const int blocks = (int)((nvec + 255) / 256 > 16384 ? 16384 : (nvec + 255) / 256);
-        hipLaunchKernelGGL(affine_act_res_kernel<4>, dim3(blocks), dim3(256), 0, s, y, scale, shift, res,
-                           out, nvec, C, T, act, leak, amax_dst, bm_fastdiv((unsigned)(T / 4)), bm_fastdiv((unsigned)C));
-        nblk = blocks;
-    } else {
-        const int blocks = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-        hipLaunchKernelGGL(affine_act_res_kernel<1>, dim3(blocks), dim3(256), 0, s, y, scale, shift, res,
-                           out, n, C, T, act, leak, amax_dst, bm_fastdiv((unsigned)T), bm_fastdiv((unsigned)C));
-        nblk = blocks;
-    }
+    const int vec = T % 4 == 0 ? 4 : 1;
+    const long nvec = n / vec;
+    const int nblk = flat_blocks(nvec);
+    LAUNCH_VEC(vec == 4, affine_act_res_kernel, dim3(nblk), s, y, scale, shift, res, out, nvec, C, T, act, leak, amax_dst,
+               bm_fastdiv((unsigned)(T / vec)), bm_fastdiv((unsigned)C));
     if (int rc = bm_check_launch("affine_act_res")) return rc;
     return bm_amax_done(amax_dst, nblk, amax_out, s);
 }
@@ -215,9 +266,11 @@ extern "C" int bm_affine_act_res(const float* y, const float* scale, const float
 // Pass 1 (bn_bwd_reduce): per-(channel, split) partial sums.  Pass 2 (bn_bwd_apply): dy + sum(dy).
 // ------------------------------------------------------------------------------------------------
 #define NSPLIT_MAX 32
-#ifndef BWD_UNROLL
-#define BWD_UNROLL 4      // slab positions per loop trip of the backward kernels (see bn_bwd_reduce_kernel)
-#endif
+
+// a slab position of the two-pass kernels: where it is, and the vectors of dout and y there
+template <int VEC> struct BnPos { Pack<VEC> d, v; };
+#define BN_POS_AT(bl, tv) (((long)(sl.b0 + (bl)) * C + c) * T + (long)(tv) * VEC)
+#define BN_POS_LOAD(p, off, unused) p.d = Pack<VEC>::ld(dout + off); p.v = Pack<VEC>::ld(y + off)
 
 template <int VEC>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
@@ -226,42 +279,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     double* __restrict__ partial, int B, int C, int T, int act, float leak) {
     __shared__ double sh[4 * 2];
     const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const int TV = T / VEC;
+    const Slab sl(B, split, nsplit, T, VEC);
     const float sc = scale ? scale[c] : 1.f, shf = scale ? shift[c] : 0.f;
     const float mu = mean ? mean[c] : 0.f, is = invstd ? invstd[c] : 1.f;
-    double acc[2] = {0, 0};
     float s0 = 0.f, s1 = 0.f;
-    const int nb = b1 - b0;
-    // BWD_UNROLL positions per trip, all loads issued before the first use: two 16-byte loads in flight per thread
-    // left these (channel, split) kernels latency-bound at ~5.0 TB/s (the flat-grid forward kernels reach 5.8-6.0)
-    SlabWalk w(TV, threadIdx.x, blockDim.x);
-    while (w.bl < nb) {
-        long off[BWD_UNROLL];
-        bool ok[BWD_UNROLL];
-        Pack<VEC> d[BWD_UNROLL], v[BWD_UNROLL];
+    SLAB_TRIPS_BEGIN(sl, BN_POS_AT, BnPos<VEC>, BN_POS_LOAD)
+        const BnPos<VEC>& p = data[q];
 #pragma unroll
-        for (int u = 0; u < BWD_UNROLL; ++u) {
-            // (unconditional loads -- a position past the slab re-reads the trip's first one -- so that nothing but
-            // the address arithmetic sits between the 2 * BWD_UNROLL loads)
-            ok[u] = w.bl < nb;
-            off[u] = ok[u] ? ((long)(b0 + w.bl) * C + c) * T + (long)w.tv * VEC : off[0];
-            d[u] = Pack<VEC>::ld(dout + off[u]);
-            v[u] = Pack<VEC>::ld(y + off[u]);
-            if (ok[u]) w.next();
+        for (int i = 0; i < VEC; ++i) {
+            const float dz = p.d.v[i] * bm_act_grad(p.v.v[i] * sc + shf, act, leak);
+            s0 += dz;
+            s1 += dz * ((p.v.v[i] - mu) * is);
         }
-#pragma unroll
-        for (int u = 0; u < BWD_UNROLL; ++u) {
-            if (!ok[u]) continue;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float dz = d[u].v[i] * bm_act_grad(v[u].v[i] * sc + shf, act, leak);
-                s0 += dz;
-                s1 += dz * ((v[u].v[i] - mu) * is);
-            }
-        }
-    }
-    acc[0] = s0; acc[1] = s1;
+    SLAB_TRIPS_END
+    double acc[2] = {s0, s1};
     block_sum<2>(acc, sh);
     if (threadIdx.x == 0) {
         partial[((long)c * nsplit + split) * 2 + 0] = acc[0];
@@ -282,8 +313,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     // `reverse`: walk the batch splits in the opposite order of the reduce pass that has just streamed the same two
     // tensors -- what that pass read last is what the memory-side cache still holds (236 of its 256 MB)
     const int c = blockIdx.x, nsplit = gridDim.y, split = reverse ? nsplit - 1 - (int)blockIdx.y : (int)blockIdx.y;
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const int TV = T / VEC;
+    const Slab sl(B, split, nsplit, T, VEC);
     const float sc = scale ? scale[c] : 1.f, shf = scale ? shift[c] : 0.f;
     const float mu = mean ? mean[c] : 0.f, is = invstd ? invstd[c] : 1.f;
     float k1 = 0.f, k2 = 0.f;
@@ -304,39 +334,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
         }
     }
     float sdy = 0.f;
-    const int nb = b1 - b0;
-    SlabWalk w(TV, threadIdx.x, blockDim.x);
-    while (w.bl < nb) {
-        long off[BWD_UNROLL];
-        bool ok[BWD_UNROLL];
-        Pack<VEC> d[BWD_UNROLL], v[BWD_UNROLL];
+    SLAB_TRIPS_BEGIN(sl, BN_POS_AT, BnPos<VEC>, BN_POS_LOAD)
+        const BnPos<VEC>& p = data[q];
+        Pack<VEC> o;
 #pragma unroll
-        for (int u = 0; u < BWD_UNROLL; ++u) {
-            // (unconditional loads -- a position past the slab re-reads the trip's first one -- so that nothing but
-            // the address arithmetic sits between the 2 * BWD_UNROLL loads)
-            ok[u] = w.bl < nb;
-            off[u] = ok[u] ? ((long)(b0 + w.bl) * C + c) * T + (long)w.tv * VEC : off[0];
-            d[u] = Pack<VEC>::ld(dout + off[u]);
-            v[u] = Pack<VEC>::ld(y + off[u]);
-            if (ok[u]) w.next();
+        for (int i = 0; i < VEC; ++i) {
+            const float dz = p.d.v[i] * bm_act_grad(p.v.v[i] * sc + shf, act, leak);
+            float g = dz;
+            if (bn_train) g = sc * (dz - k1 - ((p.v.v[i] - mu) * is) * k2);
+            else if (scale) g = sc * dz;
+            o.v[i] = g;
+            sdy += g;
+            amx = fmaxf(amx, fabsf(g));
         }
-#pragma unroll
-        for (int u = 0; u < BWD_UNROLL; ++u) {
-            if (!ok[u]) continue;
-            Pack<VEC> o;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float dz = d[u].v[i] * bm_act_grad(v[u].v[i] * sc + shf, act, leak);
-                float g = dz;
-                if (bn_train) g = sc * (dz - k1 - ((v[u].v[i] - mu) * is) * k2);
-                else if (scale) g = sc * dz;
-                o.v[i] = g;
-                sdy += g;
-                amx = fmaxf(amx, fabsf(g));
-            }
-            o.st(dy + off[u]);
-        }
-    }
+        o.st(dy + off[q]);
+    SLAB_TRIPS_END
     bm_publish_amax(amx, amax_ws, amax_sh);
     double acc[1] = {(double)sdy};
     block_sum<1>(acc, sh);
@@ -394,24 +406,23 @@ __global__ __launch_bounds__(256, 4) void bn_bwd_fused_kernel(
     // consecutive workgroups = the splits of one channel (they start together under the observed dispatch order; the
     // protocol does not depend on it)
     const int c = (int)bm_div(blockIdx.x, div_ns), split = (int)(blockIdx.x - (unsigned)c * (unsigned)nsplit);
-    const int TV = T / 4;
     const float sc = scale[c], shf = shift[c], mu = mean[c], is = invstd[c];
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const unsigned nvec = (unsigned)(b1 - b0) * (unsigned)TV;            // <= 256 * MAXIT (host check)
+    const Slab sl(B, split, nsplit, T, 4);
+    const unsigned nvec = (unsigned)sl.nb * (unsigned)sl.TV;             // <= 256 * MAXIT (host check)
 
     // phase 1: the slab into registers, all loads in flight before the first use
     float4 d[MAXIT], v[MAXIT];
-    // element offset of position `it` of this thread (B * C * T < 2^32, host check); recomputed for the stores of phase 2
-    // rather than kept: MAXIT registers decide between 4 and 3 workgroups per CU
-    auto offset = [&](int it) {
+    // element offset of position `it` of this thread in the slab `s` of this channel (B * C * T < 2^32, host check);
+    // recomputed for the stores of phase 2 rather than kept: MAXIT registers decide between 4 and 3 workgroups per CU
+    auto offset = [&](const Slab& s, int it) {
         const unsigned e = (unsigned)it * 256u + threadIdx.x;
-        const unsigned ee = e < nvec ? e : 0u;                           // past the slab: re-read position 0 (unused)
+        const unsigned ee = e < (unsigned)s.nb * (unsigned)s.TV ? e : 0u;    // past the slab: re-read position 0 (unused)
         const unsigned bl = bm_div(ee, div_tv);
-        return ((unsigned)(b0 + (int)bl) * (unsigned)C + (unsigned)c) * (unsigned)T + (ee - bl * (unsigned)TV) * 4u;
+        return ((unsigned)(s.b0 + (int)bl) * (unsigned)C + (unsigned)c) * (unsigned)T + (ee - bl * (unsigned)s.TV) * 4u;
     };
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-        const unsigned o = offset(it);
+        const unsigned o = offset(sl, it);
         d[it] = *reinterpret_cast<const float4*>(dout + o);
         v[it] = *reinterpret_cast<const float4*>(y + o);
     }
@@ -467,15 +478,11 @@ __global__ __launch_bounds__(256, 4) void bn_bwd_fused_kernel(
         if (threadIdx.x == 0) atomicAdd(&bn_fused_fallbacks, 1ull);
         for (int k = 0; k < nsplit; ++k) {
             if (!((missing >> k) & 1u)) continue;
-            const int kb0 = (int)((long)B * k / nsplit), kb1 = (int)((long)B * (k + 1) / nsplit);
-            const unsigned knvec = (unsigned)(kb1 - kb0) * (unsigned)TV;
+            const Slab ks(B, k, nsplit, T, 4);                           // split k's slab, walked as split k walks it
             float t0 = 0.f, t1 = 0.f;
             for (int it = 0; it < MAXIT; ++it) {
-                const unsigned e = (unsigned)it * 256u + threadIdx.x;
-                const bool ok = e < knvec;
-                const unsigned ee = ok ? e : 0u;
-                const unsigned bl = bm_div(ee, div_tv);
-                const unsigned o = ((unsigned)(kb0 + (int)bl) * (unsigned)C + (unsigned)c) * (unsigned)T + (ee - bl * (unsigned)TV) * 4u;
+                const bool ok = (unsigned)it * 256u + threadIdx.x < (unsigned)ks.nb * (unsigned)ks.TV;
+                const unsigned o = offset(ks, it);
                 const float4 dv = *reinterpret_cast<const float4*>(dout + o);
                 const float4 yv = *reinterpret_cast<const float4*>(y + o);
                 const float* dd = reinterpret_cast<const float*>(&dv);
@@ -526,7 +533,7 @@ __global__ __launch_bounds__(256, 4) void bn_bwd_fused_kernel(
                 sdy += g;
                 amx = fmaxf(amx, fabsf(g));
             }
-            *reinterpret_cast<float4*>(dy + offset(it)) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(dy + offset(sl, it)) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
     bm_publish_amax_at(amx, amax_ws, amax_sh, (unsigned)split * (unsigned)C + (unsigned)c);
@@ -598,9 +605,26 @@ __global__ void finalize_channel_sums_kernel(const double* __restrict__ partial,
 
 extern "C" int bm_bwd_nsplit(int B) { return B >= 64 ? 8 : (B >= 8 ? 4 : 1); }
 
+// What follows the launch `what` of a (row, split) grid that left per-(row, split) maxima in the amax workspace and
+// double sums in `sums` [rows][nsplit].  The partials are per row already: ONE launch folds them into the tensor slot,
+// the per-row maxima and the bias gradient (two-stage mode; otherwise the sums get their own launch).
+static int finish_rows(const char* what, const BmAmaxDst& amax_dst, int rows, int nsplit, int nblocks, float* amax_out,
+                       float* amax_rows_out, const double* sums, float* dbias, hipStream_t s) {
+    if (amax_dst.ws && amax_out && dbias) {
+        if (int rc = bm_check_launch(what)) return rc;
+        return bm_amax_finalize_rows_sums(amax_dst.ws, rows, nsplit, amax_out, amax_rows_out, sums, dbias, s);
+    }
+    if (dbias)
+        hipLaunchKernelGGL(finalize_channel_sums_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, s, sums, dbias, rows,
+                           nsplit);
+    if (int rc = bm_check_launch(what)) return rc;
+    if (amax_dst.ws) return bm_amax_finalize_rows(amax_dst.ws, rows, nsplit, amax_out, amax_rows_out, s);
+    return bm_amax_done(amax_dst, nblocks, amax_out, s);
+}
+
 // The backward kernels evaluate the GELU derivative with one exponential and no erf (bm_gelu_grad_fast, bm_common.h);
-// the apply pass walks the batch in the OPPOSITE order of the reduce pass (what that pass read last is what the
-// memory-side cache still holds; -0.03 ms per step, profiles/r3r_ab_bn_apply_reverse.txt).
+// the apply pass walks the batch in the OPPOSITE order of the reduce pass (`reverse`, see bn_bwd_apply_kernel: -0.03 ms
+// per step, profiles/r3r_ab_bn_apply_reverse.txt).
 static int gelu_grad_code(int act) { return act == BM_ACT_GELU ? BM_ACT_GELU_FASTGRAD : act; }
 
 // workspace: doubles, (2*C*nsplit) for the reduce partials + (C*nsplit) for the dy sums.
@@ -641,33 +665,14 @@ extern "C" int bm_act_bn_bwd(const float* dout, const float* y, const float* sca
         hipLaunchKernelGGL(bn_bwd_fused_kernel<FUSED_MAXIT>, fgrid, dim3(256), 0, s, dout, y, scale, shift, mean, invstd,
                            (unsigned long long*)partial, bn_train, dy, dy_partial, dgamma, dbeta, B, C, T, nsplit, act,
                            leak, amax_dst, bm_fastdiv((unsigned)(T / 4)), bm_fastdiv((unsigned)nsplit), g_fused_poll_limit);
-    } else if (T % 4 == 0) {
-        if (reduce)
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, grid, dim3(256), 0, s, dout, y, scale, shift, mean,
-                               invstd, partial, B, C, T, act, leak);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, grid, dim3(256), 0, s, dout, y, scale, shift, mean,
-                           invstd, partial, bn_train, dy, dy_partial, dgamma, dbeta, B, C, T, act, leak,
-                           amax_dst, 1);
     } else {
         if (reduce)
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, grid, dim3(256), 0, s, dout, y, scale, shift, mean,
-                               invstd, partial, B, C, T, act, leak);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, grid, dim3(256), 0, s, dout, y, scale, shift, mean,
-                           invstd, partial, bn_train, dy, dy_partial, dgamma, dbeta, B, C, T, act, leak,
-                           amax_dst, 1);
+            LAUNCH_VEC(T % 4 == 0, bn_bwd_reduce_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, B, C, T,
+                       act, leak);
+        LAUNCH_VEC(T % 4 == 0, bn_bwd_apply_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, bn_train, dy,
+                   dy_partial, dgamma, dbeta, B, C, T, act, leak, amax_dst, 1);
     }
-    // the (channel, split) grid's partials are per channel already: ONE launch folds them into the tensor slot, the
-    // per-channel maxima and the bias gradient (two-stage mode; otherwise the sums get their own launch)
-    if (amax_dst.ws && amax_out && dbias) {
-        if (int rc = bm_check_launch("act_bn_bwd")) return rc;
-        return bm_amax_finalize_rows_sums(amax_dst.ws, C, nsplit, amax_out, amax_rows_out, dy_partial, dbias, s);
-    }
-    if (dbias)
-        hipLaunchKernelGGL(finalize_channel_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, dy_partial,
-                           dbias, C, nsplit);
-    if (int rc = bm_check_launch("act_bn_bwd")) return rc;
-    if (amax_dst.ws) return bm_amax_finalize_rows(amax_dst.ws, C, nsplit, amax_out, amax_rows_out, s);
-    return bm_amax_done(amax_dst, C * nsplit, amax_out, s);
+    return finish_rows("act_bn_bwd", amax_dst, C, nsplit, C * nsplit, amax_out, amax_rows_out, dy_partial, dbias, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -679,13 +684,10 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
                                                           int T) {
     __shared__ double sh[4];
     const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const int TV = T / VEC;
+    const Slab sl(B, split, nsplit, T, VEC);
     float s = 0.f;
-    const int nb = b1 - b0;
-    for (SlabWalk w(TV, threadIdx.x, blockDim.x); w.bl < nb; w.next()) {
-        const int bl = w.bl, tv = w.tv;
-        const Pack<VEC> v = Pack<VEC>::ld(x + (long)(b0 + bl) * bstride + (long)c * T + (long)tv * VEC);
+    for (SlabWalk w(sl.TV, threadIdx.x, blockDim.x); w.bl < sl.nb; w.next()) {
+        const Pack<VEC> v = Pack<VEC>::ld(x + (long)(sl.b0 + w.bl) * bstride + (long)c * T + (long)w.tv * VEC);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) s += v.v[i];
     }
@@ -706,10 +708,7 @@ extern "C" int bm_channel_sum(const float* x, long bstride, float* out, void* wo
         return bm_set_error(BM_ERR_WORKSPACE, "channel_sum: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     double* partial = (double*)workspace;
-    if (T % 4 == 0 && bstride % 4 == 0)
-        hipLaunchKernelGGL(channel_sum_kernel<4>, dim3(C, nsplit), dim3(256), 0, s, x, bstride, partial, B, C, T);
-    else
-        hipLaunchKernelGGL(channel_sum_kernel<1>, dim3(C, nsplit), dim3(256), 0, s, x, bstride, partial, B, C, T);
+    LAUNCH_VEC(T % 4 == 0 && bstride % 4 == 0, channel_sum_kernel, dim3(C, nsplit), s, x, bstride, partial, B, C, T);
     hipLaunchKernelGGL(finalize_channel_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, partial, out, C,
                        nsplit);
     return bm_check_launch("channel_sum");
@@ -754,13 +753,11 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
                                                             int T) {
     __shared__ double sh[4 * 2];
     const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const int TV = T / VEC;
+    const Slab sl(B, split, nsplit, T, VEC);
     float s = 0.f, s2 = 0.f;
-    const int nb = b1 - b0;
-    for (SlabWalk w(TV, threadIdx.x, blockDim.x); w.bl < nb; w.next()) {
+    for (SlabWalk w(sl.TV, threadIdx.x, blockDim.x); w.bl < sl.nb; w.next()) {
         const int bl = w.bl, tv = w.tv;
-        const Pack<VEC> v = Pack<VEC>::ld(x + ((long)(b0 + bl) * C + c) * T + (long)tv * VEC);
+        const Pack<VEC> v = Pack<VEC>::ld(x + ((long)(sl.b0 + bl) * C + c) * T + (long)tv * VEC);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) { s += v.v[i]; s2 += v.v[i] * v.v[i]; }
     }
@@ -778,10 +775,7 @@ extern "C" int bm_channel_stats(const float* x, float* stats, int B, int C, int 
     BM_REQUIRE(x && stats, "channel_stats: null pointer");
     const int nsplit = bm_channel_stats_splits(B);
     hipStream_t s = (hipStream_t)stream;
-    if (T % 4 == 0)
-        hipLaunchKernelGGL(channel_stats_kernel<4>, dim3(C, nsplit), dim3(256), 0, s, x, stats, B, C, T);
-    else
-        hipLaunchKernelGGL(channel_stats_kernel<1>, dim3(C, nsplit), dim3(256), 0, s, x, stats, B, C, T);
+    LAUNCH_VEC(T % 4 == 0, channel_stats_kernel, dim3(C, nsplit), s, x, stats, B, C, T);
     return bm_check_launch("channel_stats");
 }
 
@@ -819,24 +813,24 @@ extern "C" int bm_glu_fwd(const float* u, float* out, int B, int H, int T, float
     BM_REQUIRE(n < 0xffffffffL && (long)H * T < 0xffffffffL, "glu_fwd: tensor of %ld elements (32-bit element index)", n);
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    int nblk = 0;
-    if (T % 4 == 0) {
-        const long nvec = n / 4;
-        const int blocks = (int)((nvec + 255) / 256 > 16384 ? 16384 : (nvec + 255) / 256);
-        hipLaunchKernelGGL(glu_fwd_kernel<4>, dim3(blocks), dim3(256), 0, s, u, out, nvec, H, T, amax_dst,
-                           bm_fastdiv((unsigned)((long)H * (T / 4))));
-        nblk = blocks;
-    } else {
-        const int blocks = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-        hipLaunchKernelGGL(glu_fwd_kernel<1>, dim3(blocks), dim3(256), 0, s, u, out, n, H, T, amax_dst,
-                           bm_fastdiv((unsigned)((long)H * T)));
-        nblk = blocks;
-    }
+    const int vec = T % 4 == 0 ? 4 : 1;
+    const long nvec = n / vec;
+    const int nblk = flat_blocks(nvec);
+    LAUNCH_VEC(vec == 4, glu_fwd_kernel, dim3(nblk), s, u, out, nvec, H, T, amax_dst,
+               bm_fastdiv((unsigned)((long)H * (T / vec))));
     if (int rc = bm_check_launch("glu_fwd")) return rc;
     return bm_amax_done(amax_dst, nblk, amax_out, s);
 }
 
 // du_a = dout * sig(g) ; du_g = dout * a * sig(g) * (1 - sig(g)); also per-channel sums (bias grad).
+// A slab position: the offsets of the value row in u / du and of the row in dout, and the three vectors read there.
+template <int VEC> struct GluPos { Pack<VEC> d, a, g; };
+#define GLU_POS_AT_U(bl, tv) (((long)(sl.b0 + (bl)) * 2 * H + hch) * T + (long)(tv) * VEC)
+#define GLU_POS_AT_DOUT(bl, tv) (((long)(sl.b0 + (bl)) * H + hch) * T + (long)(tv) * VEC)
+#define GLU_POS_LOAD(p, offu, offd)     \
+    p.d = Pack<VEC>::ld(dout + offd);   \
+    p.a = Pack<VEC>::ld(u + offu);      \
+    p.g = Pack<VEC>::ld(u + offu + (long)H * T)
 template <int VEC>
 __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ dout,
                                                       const float* __restrict__ u, float* __restrict__ du,
@@ -846,45 +840,24 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ 
     __shared__ float amax_sh[4];
     float amx = 0.f, amx_g = 0.f;                      // max |du| of the value row hch and of the gate row H + hch
     const int hch = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
-    const int b0 = (int)((long)B * split / nsplit), b1 = (int)((long)B * (split + 1) / nsplit);
-    const int TV = T / VEC;
+    const Slab sl(B, split, nsplit, T, VEC);
     float sa = 0.f, sg = 0.f;
-    const int nb = b1 - b0;
-    SlabWalk w(TV, threadIdx.x, blockDim.x);
-    while (w.bl < nb) {
-        long offa[BWD_UNROLL];
-        bool ok[BWD_UNROLL];
-        Pack<VEC> d[BWD_UNROLL], a[BWD_UNROLL], g[BWD_UNROLL];
-        long offo[BWD_UNROLL];
+    SLAB_TRIPS_BEGIN2(sl, GLU_POS_AT_U, GLU_POS_AT_DOUT, GluPos<VEC>, GLU_POS_LOAD)
+        const GluPos<VEC>& p = data[q];
+        Pack<VEC> oa, og;
 #pragma unroll
-        for (int q = 0; q < BWD_UNROLL; ++q) {
-            ok[q] = w.bl < nb;
-            const int b = b0 + w.bl;
-            offa[q] = ok[q] ? ((long)b * 2 * H + hch) * T + (long)w.tv * VEC : offa[0];
-            offo[q] = ok[q] ? ((long)b * H + hch) * T + (long)w.tv * VEC : offo[0];
-            d[q] = Pack<VEC>::ld(dout + offo[q]);
-            a[q] = Pack<VEC>::ld(u + offa[q]);
-            g[q] = Pack<VEC>::ld(u + offa[q] + (long)H * T);
-            if (ok[q]) w.next();
+        for (int i = 0; i < VEC; ++i) {
+            const float sgm = 1.f / (1.f + expf(-p.g.v[i]));
+            oa.v[i] = p.d.v[i] * sgm;
+            og.v[i] = p.d.v[i] * p.a.v[i] * sgm * (1.f - sgm);
+            sa += oa.v[i];
+            sg += og.v[i];
+            amx = fmaxf(amx, fabsf(oa.v[i]));
+            amx_g = fmaxf(amx_g, fabsf(og.v[i]));
         }
-#pragma unroll
-        for (int q = 0; q < BWD_UNROLL; ++q) {
-            if (!ok[q]) continue;
-            Pack<VEC> oa, og;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float sgm = 1.f / (1.f + expf(-g[q].v[i]));
-                oa.v[i] = d[q].v[i] * sgm;
-                og.v[i] = d[q].v[i] * a[q].v[i] * sgm * (1.f - sgm);
-                sa += oa.v[i];
-                sg += og.v[i];
-                amx = fmaxf(amx, fabsf(oa.v[i]));
-                amx_g = fmaxf(amx_g, fabsf(og.v[i]));
-            }
-            oa.st(du + offa[q]);
-            og.st(du + offa[q] + (long)H * T);
-        }
-    }
+        oa.st(du + off[q]);
+        og.st(du + off[q] + (long)H * T);
+    SLAB_TRIPS_END
     if (amax_ws.ws) {
         // two-stage mode: one partial per ROW of du, laid out [nsplit][2 H] (per-channel maxima, see bm_glu_bwd)
         bm_publish_amax_at(amx, amax_ws, amax_sh, (unsigned)(split * 2 * H + hch));
@@ -918,20 +891,6 @@ extern "C" int bm_glu_bwd(const float* dout, const float* u, float* du, float* d
     double* partial = (double*)workspace;
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    if (T % 4 == 0)
-        hipLaunchKernelGGL(glu_bwd_kernel<4>, dim3(H, nsplit), dim3(256), 0, s, dout, u, du, partial, B, H, T,
-                           amax_dst);
-    else
-        hipLaunchKernelGGL(glu_bwd_kernel<1>, dim3(H, nsplit), dim3(256), 0, s, dout, u, du, partial, B, H, T,
-                           amax_dst);
-    if (amax_dst.ws && amax_out && dbias) {
-        if (int rc = bm_check_launch("glu_bwd")) return rc;
-        return bm_amax_finalize_rows_sums(amax_dst.ws, 2 * H, nsplit, amax_out, amax_rows_out, partial, dbias, s);
-    }
-    if (dbias)
-        hipLaunchKernelGGL(finalize_channel_sums_kernel, dim3(cdiv(2 * H, 256)), dim3(256), 0, s, partial,
-                           dbias, 2 * H, nsplit);
-    if (int rc = bm_check_launch("glu_bwd")) return rc;
-    if (amax_dst.ws) return bm_amax_finalize_rows(amax_dst.ws, 2 * H, nsplit, amax_out, amax_rows_out, s);
-    return bm_amax_done(amax_dst, H * nsplit, amax_out, s);
+    LAUNCH_VEC(T % 4 == 0, glu_bwd_kernel, dim3(H, nsplit), s, dout, u, du, partial, B, H, T, amax_dst);
+    return finish_rows("glu_bwd", amax_dst, 2 * H, nsplit, H * nsplit, amax_out, amax_rows_out, partial, dbias, s);
 }

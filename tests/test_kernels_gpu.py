@@ -229,6 +229,89 @@ def test_one_pass_batchnorm_backward_against_the_two_pass_kernels(H, B, C, T, tr
         assert rel_l2(got[1], (dz * xh).sum((0, 2))) < GRAD_TOL and rel_l2(got[2], dz.sum((0, 2))) < GRAD_TOL, name
 
 
+@pytest.mark.parametrize("B,C,T", [(67, 3, 79),      # dword path; 8 and 16 ragged splits of 8-9 and 4-5 segments
+                                   (67, 3, 44),      # vector path, 11 vectors per row; a slab shorter than one trip
+                                   (9, 2, 1028),     # 4 splits; 257 vectors per row: the walk's step wraps a row each time
+                                   (70, 2, 2052),    # 513 vectors per row; ~18 trips, the last one partly past the slab
+                                   (1, 5, 4)])       # one split, one vector
+def test_slab_walk_of_the_channel_split_kernels(H, B, C, T):
+    """The (channel, split) streaming kernels -- channel_sum, channel_stats, glu_bwd and the two-pass act_bn_bwd -- walk
+    their slab of the batch in the same way (and glu_fwd its flat grid): against fp64 on shapes where that walk can go
+    wrong (ragged splits, rows that are no multiple of the workgroup, trips that end past the slab), with the published
+    maxima exact and the bits equal from run to run."""
+    from brainmagick_amd._lib import lib
+    g = _gen(B * 7 + C * 3 + T)
+    y = torch.randn(B, C, T, generator=g) * 1.5 + 0.3
+    dout = torch.randn(B, C, T, generator=g)
+    u = torch.randn(B, 2 * C, T, generator=g) * 1.5
+    yd, dd, ud = y.double(), dout.double(), u.double()
+    yg, dg, ug = y.cuda(), dout.cuda(), u.cuda()
+
+    def maxima_are_exact(t, what):
+        assert float(H.amax(t).max()) == float(t.abs().max()), what
+        rows = H.row_amax_of(t)                 # None in the compute modes that publish no row maxima
+        if rows is not None:
+            assert torch.equal(rows.cpu(), t.abs().amax((0, 2)).cpu()), what
+
+    assert rel_l2(H.channel_sum(yg), yd.sum((0, 2))) < GRAD_TOL
+    assert torch.equal(H.channel_sum(yg), H.channel_sum(yg))
+    stats = H.channel_stats(yg)
+    assert stats.shape[0] == lib().bm_channel_stats_splits(B)
+    folded = stats.double().sum(0)
+    assert rel_l2(folded[:, 0], yd.sum((0, 2))) < 1e-5
+    assert rel_l2(folded[:, 1], (yd ** 2).sum((0, 2))) < 1e-5
+    assert torch.equal(stats, H.channel_stats(yg))
+
+    sig = torch.sigmoid(ud[:, C:])
+    out = H.glu_fwd(ug)
+    assert rel_l2(out, ud[:, :C] * sig) < FWD_TOL
+    assert torch.equal(out, H.glu_fwd(ug))
+    du_ref = torch.cat([dd * sig, dd * ud[:, :C] * sig * (1 - sig)], 1)
+    du, dbias = H.glu_bwd(dg, ug)
+    assert rel_l2(du, du_ref) < GRAD_TOL
+    assert rel_l2(dbias, du_ref.sum((0, 2))) < GRAD_TOL
+    maxima_are_exact(du, "glu_bwd")
+    du2, dbias2 = H.glu_bwd(dg, ug)
+    assert torch.equal(du, du2) and torch.equal(dbias, dbias2)
+
+    gamma = torch.rand(C, generator=g) + 0.5
+    beta = torch.randn(C, generator=g)
+    mean = yd.mean((0, 2))
+    invstd = 1.0 / torch.sqrt(yd.var((0, 2), unbiased=False) + 1e-5)
+    scale = gamma.double() * invstd
+    shift = beta.double() - mean * scale
+    bn = [t.float().cuda() for t in (scale, shift, mean, invstd)]
+
+    def gelu_grad(z):
+        return 0.5 * (1 + torch.erf(z / math.sqrt(2))) + z * torch.exp(-0.5 * z * z) / math.sqrt(2 * math.pi)
+    dz = dd * gelu_grad(yd * scale[None, :, None] + shift[None, :, None])
+    xh = (yd - mean[None, :, None]) * invstd[None, :, None]
+    n = B * T
+    sc = scale[None, :, None]
+    cases = {"train": (bn, True, True,
+                       sc * (dz - dz.sum((0, 2), keepdim=True) / n - xh * (dz * xh).sum((0, 2), keepdim=True) / n)),
+             "eval": (bn, False, True, sc * dz),
+             "no BatchNorm": ([None] * 4, False, False, dd * gelu_grad(yd))}
+    prev = lib().bm_act_bn_bwd_set_fused(0)          # the two-pass kernels: bn_bwd_reduce + bn_bwd_apply
+    try:
+        for name, (stats4, train, affine, ref) in cases.items():
+            dy, dgamma, dbeta, dbias = H.act_bn_bwd(dg, yg, *stats4, train, H.ACT_GELU, want_affine_grads=affine)
+            assert rel_l2(dy, ref) < GRAD_TOL, name
+            if affine:
+                assert rel_l2(dgamma, (dz * xh).sum((0, 2))) < GRAD_TOL, name
+                assert rel_l2(dbeta, dz.sum((0, 2))) < GRAD_TOL, name
+            if train:
+                assert float(dbias.abs().max()) < 1e-2 * max(1.0, float(dy.abs().max())), name   # sum(dy) of a BN input is ~0
+            else:
+                assert rel_l2(dbias, ref.sum((0, 2))) < GRAD_TOL, name
+            maxima_are_exact(dy, name)
+            again = H.act_bn_bwd(dg, yg, *stats4, train, H.ACT_GELU, want_affine_grads=affine)
+            for a, b in zip((dy, dgamma, dbeta, dbias), again):
+                assert a is None or torch.equal(a, b), name
+    finally:
+        lib().bm_act_bn_bwd_set_fused(prev)
+
+
 @pytest.mark.parametrize("T", [360, 343])
 @pytest.mark.parametrize("act", ["gelu", "relu", "leaky"])
 def test_batchnorm_act_residual(H, T, act):
