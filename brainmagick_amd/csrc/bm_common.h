@@ -67,7 +67,9 @@ __device__ __forceinline__ int bm_xcd_remap(int id, int n) {
     return base + slot;
 }
 
-// Activations used by SimpleConv (bm/models/simpleconv.py:85-90).
+// Activations used by SimpleConv (bm/models/simpleconv.py:85-90).  A NaN propagates like the reference's: F.relu(nan) is
+// nan (torch's threshold keeps what is not <= 0), and so is its derivative's pass-through of the incoming gradient --
+// hence `!(z <= 0)` where `z > 0` would turn a NaN into 0; bit-identical for every other input, -0 included.
 enum { BM_ACT_NONE = 0, BM_ACT_GELU = 1, BM_ACT_RELU = 2, BM_ACT_LEAKY = 3 };
 
 // erf: the library erff.  (A branch-free evaluation of both minimax polynomials of a faithfully-rounded erff --
@@ -77,7 +79,7 @@ __device__ __forceinline__ float bm_erff(float a) { return erff(a); }
 
 __device__ __forceinline__ float bm_act(float z, int act, float leak) {
     if (act == BM_ACT_GELU) return 0.5f * z * (1.0f + bm_erff(z * 0.70710678118654752440f));
-    if (act == BM_ACT_RELU) return z > 0.f ? z : 0.f;
+    if (act == BM_ACT_RELU) return !(z <= 0.f) ? z : 0.f;
     if (act == BM_ACT_LEAKY) return z > 0.f ? z : z * leak;
     return z;
 }
@@ -115,7 +117,7 @@ __device__ __forceinline__ float bm_act_grad(float z, int act, float leak) {
         const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
         return cdf + z * pdf;
     }
-    if (act == BM_ACT_RELU) return z > 0.f ? 1.f : 0.f;
+    if (act == BM_ACT_RELU) return !(z <= 0.f) ? 1.f : 0.f;
     if (act == BM_ACT_LEAKY) return z > 0.f ? 1.f : leak;
     return 1.f;
 }

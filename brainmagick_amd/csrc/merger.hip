@@ -50,7 +50,8 @@ extern "C" int bm_fourier_emb(const float* positions, float* emb, long rows, int
 
 // weights[u][o][:] = softmax_c(scores[u][o][c] + offset[u][c]); offset = -inf for INVALID sensors
 // (both coordinates == -0.1, common.py:235-236,340) and, when ban_radius > 0, for sensors within
-// ban_radius of the ban centre (common.py:342-346).  An all-masked row yields NaN like the reference.
+// ban_radius of the ban centre (common.py:342-346).  An all-masked row yields NaN like the reference, and so does a
+// row with a NaN (or +inf) score under a masked sensor: the offset is ADDED, as the reference does (common.py:356).
 __global__ void masked_softmax_kernel(const float* __restrict__ scores, const float* __restrict__ pos,
                                       const float* __restrict__ ban_center, float ban_radius,
                                       float* __restrict__ weights, int U, int O, int C) {
@@ -70,7 +71,7 @@ __global__ void masked_softmax_kernel(const float* __restrict__ scores, const fl
             const float dx = __fsub_rn(px, cx), dy = __fsub_rn(py, cy);
             masked = masked || (sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))) <= ban_radius);
         }
-        const float s = masked ? -INFINITY : sr[c];
+        const float s = sr[c] + (masked ? -INFINITY : 0.f);
         mx = fmaxf(mx, s);
     }
     mx = bm_wave_max(mx);
@@ -82,7 +83,7 @@ __global__ void masked_softmax_kernel(const float* __restrict__ scores, const fl
             const float dx = __fsub_rn(px, cx), dy = __fsub_rn(py, cy);
             masked = masked || (sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))) <= ban_radius);
         }
-        const float s = masked ? -INFINITY : sr[c];
+        const float s = sr[c] + (masked ? -INFINITY : 0.f);
         const float e = expf(s - mx);          // (-inf) - (-inf) = NaN for an all-masked row
         weights[row * C + c] = e;
         sum += e;

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(RG_THREADS) void regress_bwd_kernel(const float* __
             const bool sel = mask_mode == RG_MASK_NONE || rg_get(m, i) != 0;
             const float d = rg_get(e, i) - rg_get(o, i);
             float v;
-            if (kind == RG_L1) v = d > 0.f ? scale : d < 0.f ? -scale : d == 0.f ? 0.f : d;   // sign(0) = 0; NaN stays
+            if (kind == RG_L1) v = d > 0.f ? scale : d < 0.f ? -scale : 0.f;   // torch's sign: (0 < d) - (d < 0), 0 for 0 AND for NaN
             else v = d * scale * g;
             v = sel ? v : 0.f;
             rg_set(r, i, v);

@@ -6,6 +6,9 @@
 // The reference does this with a host loop + `.item()` per segment; here the recording index is a
 // device tensor, the centre/scale tables live in HBM as [R][C], and max|x| per segment is an
 // order-independent atomic max (deterministic).  fp32 op order = the reference's (sub, then div).
+// Non-finite samples behave like the reference's: `clamp_` keeps a NaN (and turns +-inf into +-limit), so the
+// finiteness check behind this kernel still sees it; max|x| of a segment that holds a NaN is NaN like torch's `max`,
+// so `max > limit` is false and ScaleReject keeps the segment (bm/norm.py:334-335).
 #include "bm_common.h"
 
 template <int VEC>
@@ -17,7 +20,7 @@ __global__ void center_scale_kernel(const float* __restrict__ x, float* __restri
     const int b = blockIdx.y;
     const long g = group ? group[b] : 0;
     const int TV = T / VEC;
-    float local_max = 0.f;
+    unsigned local_max = 0u;      // bit pattern of max |r|: non-negative floats order like their bits, and a NaN above them all
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < C * TV; e += gridDim.x * blockDim.x) {
         const int c = e / TV;
         const int tv = e - c * TV;
@@ -33,8 +36,8 @@ __global__ void center_scale_kernel(const float* __restrict__ x, float* __restri
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             float r = __fdiv_rn(__fsub_rn(v[i], ce), sc);
-            if (clip) r = fminf(fmaxf(r, -limit), limit);
-            local_max = fmaxf(local_max, fabsf(r));
+            if (clip) r = r > limit ? limit : (r < -limit ? -limit : r);      // keeps a NaN (fminf / fmaxf would drop it)
+            local_max = max(local_max, __float_as_uint(fabsf(r)));
             v[i] = r;
         }
         if constexpr (VEC == 4) {
@@ -44,9 +47,9 @@ __global__ void center_scale_kernel(const float* __restrict__ x, float* __restri
         }
     }
     if (maxabs_bits) {
-        local_max = bm_wave_max(local_max);
-        // non-negative floats order like their bit patterns
-        if ((threadIdx.x & 63) == 0) atomicMax(&maxabs_bits[b], __float_as_uint(local_max));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) local_max = max(local_max, (unsigned)__shfl_xor((int)local_max, o));
+        if ((threadIdx.x & 63) == 0) atomicMax(&maxabs_bits[b], local_max);
     }
 }
 
