@@ -299,7 +299,16 @@ extern "C" int bm_clip_ce_cols(const float* scores, const float* inv_norm, float
 // top-k columns of every probability / score row and "is the row's label among the labels of its
 // top-k candidates".  One wavefront per row; k selection passes, each a strided scan + wave arg-max
 // (ties broken towards the lower column index), no per-lane candidate lists (k stays in SGPR-land).
+// The order is torch.sort(descending, stable)'s (include/bm_hip.h): NaN above +inf, -0 equal to +0.
 // ------------------------------------------------------------------------------------------------
+// A key that is monotone in that order.  No value has key 0: it stands for "nothing left".
+__device__ __forceinline__ unsigned topk_key(float v) {
+    if (v != v) return 0xffffffffu;                     // NaN: the largest
+    if (v == 0.f) return 0x80000000u;                   // -0 and +0 tie
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 __global__ void topk_rows_kernel(const float* __restrict__ x, int rows, int cols, int k,
                                  int* __restrict__ idx_out, float* __restrict__ val_out,
                                  const long* __restrict__ col_labels, const long* __restrict__ row_labels,
@@ -308,28 +317,28 @@ __global__ void topk_rows_kernel(const float* __restrict__ x, int rows, int cols
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* xr = x + (long)row * cols;
-    float prev_v = INFINITY;
+    unsigned prev_v = 0xffffffffu;
     int prev_i = -1;
     int hit = 0;
     const long want = row_labels ? row_labels[row] : 0;
     for (int p = 0; p < k; ++p) {
-        float best_v = -INFINITY;
+        unsigned best_v = 0u;
         int best_i = cols;               // sentinel: nothing left
         for (int c = lane; c < cols; c += 64) {
-            const float v = xr[c];
+            const unsigned v = topk_key(xr[c]);
             const bool eligible = (v < prev_v) || (v == prev_v && c > prev_i);
             if (eligible && (v > best_v || (v == best_v && c < best_i))) { best_v = v; best_i = c; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best_v, o);
+            const unsigned ov = __shfl_xor(best_v, o);
             const int oi = __shfl_xor(best_i, o);
             if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
         }
         if (best_i >= cols) best_i = -1;  // fewer than k columns
         if (lane == 0) {
             if (idx_out) idx_out[(long)row * k + p] = best_i;
-            if (val_out) val_out[(long)row * k + p] = best_v;
+            if (val_out) val_out[(long)row * k + p] = best_i >= 0 ? xr[best_i] : -INFINITY;
         }
         if (best_i >= 0 && col_labels && col_labels[best_i] == want) hit = 1;
         prev_v = best_v;

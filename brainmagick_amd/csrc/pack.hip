@@ -93,10 +93,17 @@ __global__ void group_by_index_kernel(const long* __restrict__ idx, int B, int G
     }
 }
 
+#define BM_GROUP_MAX_INTS (64 * 1024 / 4)
+
 extern "C" int bm_group_by_index(const long* idx, int B, int G, int* order, int* seg, int* err_flag,
                                  void* stream) {
-    BM_REQUIRE(idx && order && seg, "group_by_index: null pointer");
-    BM_REQUIRE(B >= 0 && B <= 16000 && G > 0 && G <= 16000, "group_by_index: bad dims B=%d G=%d", B, G);
+    BM_REQUIRE(seg && ((idx && order) || B == 0), "group_by_index: null pointer");      // (an empty batch has no buffers)
+    BM_REQUIRE(B >= 0 && G > 0, "group_by_index: bad dims B=%d G=%d", B, G);
+    // (G + 1 + B) ints of dynamic LDS.  A launch may ask for hipDeviceProp_t::sharedMemPerBlock = 64 KiB of it; more
+    // (up to sharedMemPerBlockOptin, the CU's 160 KiB) only after hipFuncSetAttribute(...MaxDynamicSharedMemorySize),
+    // as the MFMA kernels of this library do.  This kernel does not opt in: B + G <= 16 383.
+    BM_REQUIRE((long)G + 1 + B <= BM_GROUP_MAX_INTS, "group_by_index: B + G + 1 = %ld ints of LDS exceed the %d of a "
+               "launch (B=%d G=%d)", (long)G + 1 + B, BM_GROUP_MAX_INTS, B, G);
     hipLaunchKernelGGL(group_by_index_kernel, dim3(1), dim3(256), (size_t)(G + 1 + B) * sizeof(int),
                        (hipStream_t)stream, idx, B, G, order, seg, err_flag);
     return bm_check_launch("group_by_index");
@@ -118,7 +125,7 @@ __global__ void index_to_i32_kernel(const long* __restrict__ idx, int B, int G, 
 }
 
 extern "C" int bm_index_to_i32(const long* idx, int B, int G, int* out, int* err_flag, void* stream) {
-    BM_REQUIRE(idx && out, "index_to_i32: null pointer");
+    BM_REQUIRE((idx && out) || B == 0, "index_to_i32: null pointer");
     BM_REQUIRE(B >= 0 && G > 0, "index_to_i32: bad dims B=%d G=%d", B, G);
     if (B == 0) return BM_OK;
     hipLaunchKernelGGL(index_to_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, idx, B,

@@ -41,7 +41,9 @@ long bm_packed_weight_elems(int G, int M, int Cin, int KS);
  * ConvTranspose1d(k=1) weights (simpleconv.py:189) and attention weights (common.py:357). */
 int bm_pack_weights(const float* src, float* dst, int G, int M, int Cin, int KS, long sg, long sm,
                     long sc, long sj, int flip, const float* alpha_ptr, void* stream);
-/* Stable grouping of segments by subject / layout index; replaces the gather at common.py:57. */
+/* Stable grouping of segments by subject / layout index; replaces the gather at common.py:57.  order[0 .. seg[G]) lists
+ * the segments with an index in [0, G) by group, in ascending segment order inside a group; any other index sets
+ * *err_flag and its segment is left out (the tail of `order` is then not written).  B + G <= 16 383 (64 KiB of LDS). */
 int bm_group_by_index(const long* idx, int B, int G, int* order, int* seg, int* err_flag, void* stream);
 /* int64 -> int32 group indices with a range check: out-of-range entries set *err_flag (caller raises like
  * the reference's `self.weights.gather(0, subjects...)`, bm/models/common.py:57) and are clamped to 0. */
@@ -330,7 +332,14 @@ int bm_clip_cand_coef(const float* dscaled, const float* scores, const float* in
                       const float* alpha, float* coef, int B, int Bc, void* stream);
 int bm_row_axpy_sub(float* y, const float* x, const float* coef, int rows, long K, void* stream);
 /* Retrieval evaluation: top-k columns per row + "own label among the top-k labels" hit flag.
- * Replaces probs.topk + label gather/compare of scripts/run_eval_probs.py:237-264 and bm/wer.py:104-111. */
+ * Replaces probs.topk + label gather/compare of scripts/run_eval_probs.py:237-264 and bm/wer.py:104-111.
+ * The order of a row's columns, idx_out[row][0 .. k):
+ *   - by value, descending;
+ *   - NaN ranks above +inf, as torch.topk / torch.sort rank it (an all-NaN row returns columns 0 .. k-1);
+ *   - equal values (NaN with NaN, -0 with +0) go by ascending column: torch.sort(descending, stable) cut to k;
+ *   - with k > cols the positions past `cols` hold index -1 (and value -inf); they never count as a hit.
+ * val_out holds the values of those columns, bit for bit.  hit_out[row] = 1 when col_labels[idx] == row_labels[row]
+ * (int64 compare) for any of the row's returned columns. */
 int bm_topk_rows(const float* x, int rows, int cols, int k, int* idx_out, float* val_out,
                  const long* col_labels, const long* row_labels, int* hit_out, void* stream);
 

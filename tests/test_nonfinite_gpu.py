@@ -346,6 +346,36 @@ def test_softmaxes(H):
                 lambda wd: [wd * (dw.double() - (wd * dw.double()).sum(1, keepdim=True))], GRAD_TOL)
 
 
+# ---- retrieval ---------------------------------------------------------------------------------------------------------
+def test_topk_rows(H):
+    """Nothing is computed, so nothing propagates: what matters is WHERE the plant ranks.  ``probs.topk`` puts a NaN first
+    (above +inf) and -inf last; bm_topk_rows returns torch.sort(descending, stable) cut to k (include/bm_hip.h), so a
+    row of NaN probabilities -- all sensors banned -- retrieves the same candidates here as in the reference."""
+    rows, cols = 5, 67
+    x = torch.softmax(torch.randn(rows, cols, generator=_gen(21)), 1)
+    labels = torch.arange(cols)
+    for pos in _positions(rows * cols):
+        for name, val in VALUES:
+            xp = x.clone()
+            xp.view(-1)[pos] = val
+            r, c = divmod(pos, cols)
+            for k in (1, 10, cols):
+                want = torch.sort(xp.double(), dim=1, descending=True, stable=True).indices[:, :k]
+                ref = xp.topk(k, dim=1)
+                if val != -INF:
+                    assert int(ref.indices[r, 0]) == c                   # the reference ranks NaN and +inf first
+                elif k == cols:
+                    assert int(ref.indices[r, -1]) == c
+                idx, val_k, hits = H.topk_rows(xp.cuda(), k, labels.cuda(), torch.full((rows,), c).cuda())
+                assert torch.equal(idx.cpu().long(), want), f"topk_rows k={k}: {name} at {pos}"
+                assert _same_values(val_k, ref.values), f"topk_rows k={k}: {name} at {pos}"
+                assert int(hits[r]) == (1 if val != -INF or k == cols else int(c in want[r].tolist()))
+    xp = x.clone()
+    xp[3] = NAN
+    idx, val_k, _ = H.topk_rows(xp.cuda(), 10)
+    assert idx[3].tolist() == list(range(10)) and bool(torch.isnan(val_k[3]).all()) and bool(torch.isfinite(val_k[:3]).all())
+
+
 # ---- ClipLoss ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("K", [68, 67, 1023])
 def test_clip_inv_norms(H, K):
