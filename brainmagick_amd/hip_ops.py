@@ -1080,6 +1080,83 @@ def center_scale(x: torch.Tensor, center: torch.Tensor, scale: torch.Tensor,
     return out, maxabs
 
 
+def center_scale_inverse(x: torch.Tensor, center: torch.Tensor, scale: torch.Tensor,
+                         group: tp.Optional[torch.Tensor] = None, inplace: bool = False) -> torch.Tensor:
+    """(x * scale[group[b]]) + center[group[b]], two roundings (bm/norm.py:85-86, 110-111)."""
+    _req(x, "center_scale_inverse.x")
+    _req(center, "center_scale_inverse.center")
+    _req(scale, "center_scale_inverse.scale")
+    B, C, T = x.shape
+    assert center.shape[-1] == C and scale.shape == center.shape
+    out = _touched(x) if inplace else torch.empty_like(x)
+    check(lib().bm_center_scale_inverse(_p(x), _p(out), _p(_opt(group, "group", torch.int64)), _p(center), _p(scale),
+                                        B, C, T, _stream()), "bm_center_scale_inverse")
+    return out
+
+
+MAX_QUANTILE_RANKS = 8
+MAX_CATEGORY_CARDINALITY = 16384
+CATEGORY_NOT_INTEGER, CATEGORY_MAX, CATEGORY_MIN = 1, 2, 4      # bits of category_counts' flag word
+
+
+def quantile_select(x: torch.Tensor, ranks: tp.Sequence[int]) -> torch.Tensor:
+    """out [C, Q]: the values at the (ascending) indices ``ranks`` of every column x[:, c, :] of x [N, C, T] sorted
+    ascending -- what ``torch.sort`` leaves there, NaNs last.  No host synchronisation."""
+    _req(x, "quantile_select.x")
+    if x.dim() != 3:
+        raise BmHipError(f"quantile_select: x {tuple(x.shape)} must be [N, C, T]")
+    N, C, T = x.shape
+    ranks = [int(r) for r in ranks]
+    Q = len(ranks)
+    if not 1 <= Q <= MAX_QUANTILE_RANKS:
+        raise BmHipError(f"quantile_select: 1 to {MAX_QUANTILE_RANKS} ranks, got {Q}")
+    out = torch.empty(C, Q, device=x.device, dtype=torch.float32)
+    ws = torch.zeros(lib().bm_quantile_select_workspace_bytes(C, Q), device=x.device, dtype=torch.uint8)
+    host_ranks = (ctypes.c_long * Q)(*ranks)
+    check(lib().bm_quantile_select(_p(x), ctypes.cast(host_ranks, ctypes.c_void_p), _p(out), N, C, T, Q, _p(ws),
+                                   ws.numel(), _stream()), "bm_quantile_select")
+    return out
+
+
+def masked_moments(x: torch.Tensor, mask: tp.Optional[torch.Tensor], f0: int, f1: int, per_channel: bool):
+    """(count fp64, mean fp32, std fp32), each [f1 - f0]: masked mean and unbiased std of the channels [f0, f1) of
+    x [N, F, T]; without ``per_channel`` one statistic over the whole slice, written to every channel."""
+    _req(x, "masked_moments.x")
+    if x.dim() != 3:
+        raise BmHipError(f"masked_moments: x {tuple(x.shape)} must be [N, F, T]")
+    mask, mode = _regress_mask(mask, x.shape, "masked_moments")
+    N, F, T = x.shape
+    if not 0 <= f0 < f1 <= F:
+        raise BmHipError(f"masked_moments: channel range [{f0}, {f1}) outside [0, {F})")
+    nch = f1 - f0
+    mean = torch.empty(nch, device=x.device, dtype=torch.float32)
+    std = torch.empty(nch, device=x.device, dtype=torch.float32)
+    count = torch.empty(nch, device=x.device, dtype=torch.float64)
+    ws = torch.zeros(lib().bm_masked_moments_workspace_bytes(nch), device=x.device, dtype=torch.uint8)
+    check(lib().bm_masked_moments(_p(x), _p(mask), mode, N, F, T, f0, f1, int(per_channel), _p(mean), _p(std),
+                                  _p(count), _p(ws), ws.numel(), _stream()), "bm_masked_moments")
+    return count, mean, std
+
+
+def category_counts(x: torch.Tensor, mask: tp.Optional[torch.Tensor], f: int, cardinality: int):
+    """(counts fp32 [cardinality], flags int32 [1]) of channel ``f`` of x [N, F, T]: how often every category occurs
+    among the selected values, and the CATEGORY_* bits of the reference's assert over all values."""
+    if cardinality > MAX_CATEGORY_CARDINALITY:
+        raise ValueError(f"category_counts: cardinality {cardinality} exceeds the cap of {MAX_CATEGORY_CARDINALITY} "
+                         "bins (the histogram lives in LDS)")
+    _req(x, "category_counts.x")
+    if x.dim() != 3:
+        raise BmHipError(f"category_counts: x {tuple(x.shape)} must be [N, F, T]")
+    mask, mode = _regress_mask(mask, x.shape, "category_counts")
+    N, F, T = x.shape
+    counts = torch.zeros(cardinality, device=x.device, dtype=torch.float32)
+    flags = torch.zeros(1, device=x.device, dtype=torch.int32)
+    ws = torch.zeros(lib().bm_category_counts_workspace_bytes(cardinality), device=x.device, dtype=torch.uint8)
+    check(lib().bm_category_counts(_p(x), _p(mask), mode, N, F, T, f, cardinality, _p(counts), _p(flags), _p(ws),
+                                   ws.numel(), _stream()), "bm_category_counts")
+    return counts, flags
+
+
 def row_softmax(x: torch.Tensor) -> torch.Tensor:
     _req(x, "row_softmax.x")
     y = torch.empty_like(x)

@@ -265,6 +265,37 @@ int bm_center_scale(const float* x, float* out, const long* group, const float* 
                     const float* scale, int B, int C, int T, int clip, float limit, float* maxabs,
                     void* stream);
 
+/* ---- fitting the scalers (scaler_fit.hip)  bm/norm.py:58-80,96-105,136-142,85-86,110-111 ----
+ * RobustScaler.fit (bm/norm.py:58-80 sorts one channel at a time and reads three values back): exact order statistics
+ * of every channel by an MSD radix select.  x: fp32 [N][C][T]; column c = the n = N * T values x[:, c, :]; ranks: Q <= 8
+ * ascending indices in [0, n), HOST memory; out[c][q] = the value at index ranks[q] of column c sorted ascending -- the
+ * element torch.sort leaves there (all NaNs last; -0.0 / +0.0 may come back as either zero).  Integer counting only:
+ * two runs are bit-identical.  n < 2^31.  `workspace` (bm_quantile_select_workspace_bytes) is ZEROED by the caller
+ * before every call; the launches are ordered by the stream, no workgroup waits for another. */
+long bm_quantile_select_workspace_bytes(int C, int Q);
+int bm_quantile_select(const float* x, const long* ranks, float* out, int N, int C, int T, int Q, void* workspace,
+                       long workspace_bytes, void* stream);
+/* StandardScaler.fit (bm/norm.py:96-105) on the channels [f0, f1) of x [N][F][T] under a mask (mask_mode 0 = none,
+ * 1 = bytes [N][1][T], 2 = bytes [N][F][T], as the regression kernels read them): count, mean and UNBIASED std, each
+ * [f1 - f0]; per_channel = 0 (the reference's default) computes one statistic over all selected elements of the slice
+ * and writes it to every channel.  fp64 partials folded in a fixed order, centred second walk, rounded to fp32 once.
+ * count < 2: std = NaN (torch.std); count 0: mean = NaN. */
+long bm_masked_moments_workspace_bytes(int channels);
+int bm_masked_moments(const float* x, const unsigned char* mask, int mask_mode, int N, int F, int T, int f0, int f1,
+                      int per_channel, float* mean, float* std, double* count, void* workspace, long workspace_bytes,
+                      void* stream);
+/* NoOpCategoryCountScaler.fit (bm/norm.py:136-142) on channel f of x [N][F][T]: counts[k] (fp32 like torch.histc,
+ * [cardinality], ZEROED by the caller) = number of SELECTED values equal to k; *flags = the reference's assert over ALL
+ * of the channel, masked or not: bit 1 = a value is not an integer, bit 2 = max >= cardinality, bit 4 = min != 0.
+ * cardinality <= 16 384 (LDS histogram).  `workspace` (bm_category_counts_workspace_bytes): ZEROED before every call. */
+long bm_category_counts_workspace_bytes(int cardinality);
+int bm_category_counts(const float* x, const unsigned char* mask, int mask_mode, int N, int F, int T, int f,
+                       int cardinality, float* counts, int* flags, void* workspace, long workspace_bytes, void* stream);
+/* inverse_transform (bm/norm.py:85-86, 110-111): out = (x * scale[group[b]][c]) + center[group[b]][c], two roundings
+ * like the reference's two ops; grouping as bm_center_scale.  In-place (out == x) allowed. */
+int bm_center_scale_inverse(const float* x, float* out, const long* group, const float* center, const float* scale,
+                            int B, int C, int T, void* stream);
+
 /* ---- ChannelMerger front end (merger.hip)  bm/models/common.py:239-271,334-357 ---- */
 int bm_fourier_emb(const float* positions, float* emb, long rows, int D, float margin, void* stream);
 int bm_masked_softmax(const float* scores, const float* positions, const float* ban_center,
