@@ -638,6 +638,36 @@ def test_clip_candidate_blocks_cover_the_set_below_the_addressing_limit():
         assert all(n >= 1 and n * K * 4 < 0x40000000 or n == 1 for _, n in blocks)
 
 
+def test_clip_candidate_blocks_start_exactly_at_the_limit(monkeypatch):
+    """The two sides of the threshold: one byte under the limit is one block, AT the limit the block rule applies
+    (the ``<`` in ``_candidate_blocks``); where that rule yields a single block, ``_clip_raw_scores`` still takes the
+    single-launch path."""
+    from brainmagick_amd import functional as BF
+    Bc, K = 300, 10
+    monkeypatch.setattr(BF, "_CLIP_BLOCK_BYTES", Bc * K * 4 + 1)
+    assert BF._candidate_blocks(Bc, K) == [(0, Bc)]
+    monkeypatch.setattr(BF, "_CLIP_BLOCK_BYTES", Bc * K * 4)
+    assert BF._candidate_blocks(Bc, K) == [(0, 256), (256, 44)]             # 300 rows fit: cut to a multiple of 128
+    assert BF._candidate_blocks(Bc, K + 1) == [(0, 256), (256, 44)]         # 272 rows fit
+    assert BF._candidate_blocks(Bc + 1, K) == [(0, 256), (256, 45)]
+    # under 128 rows the rule does not round: at the limit it is again the whole set, in one block
+    Bc = 100
+    monkeypatch.setattr(BF, "_CLIP_BLOCK_BYTES", Bc * K * 4)
+    assert BF._candidate_blocks(Bc, K) == [(0, Bc)]
+    assert BF._candidate_blocks(Bc + 1, K) == [(0, 100), (100, 1)]
+    calls = []
+
+    class Recorder:
+        def gemm_nt_partials(self, *a, **kw):
+            calls.append("partials")
+            return "tiles"
+
+        def __getattr__(self, name):
+            raise AssertionError(f"the single-block path called H.{name}")
+    monkeypatch.setattr(BF, "H", Recorder())
+    assert BF._clip_raw_scores(torch.zeros(4, K), torch.zeros(Bc, K), 4, Bc, K) == "tiles" and calls == ["partials"]
+
+
 def test_c_level_stdout_is_parked_on_stderr_while_a_communicator_comes_up():
     """librccl prints a version banner with printf when the first communicator is created; bench.py's contract is
     ONE JSON line on stdout.  `distrib._c_stdout_to_stderr` (wrapped around `bm_comm_init`) points fd 1 at stderr

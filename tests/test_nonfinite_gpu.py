@@ -451,6 +451,58 @@ def test_clip_ce_cols(H):
         assert bool(torch.isnan(d[:, off + j]).all()) and int(torch.isnan(d).sum()) == B
 
 
+@pytest.mark.parametrize("mode,B,Bc,Fd,T,rows,off", [
+    ("f32", 5, 30, 8, 12, 7, 12), ("f32x3", 5, 30, 8, 12, 7, 12), ("f16x2", 5, 30, 8, 12, 7, 12),
+    ("f16x2", 130, 300, 24, 77, 128, 128),      # the wide f16x2 kernels run the first two blocks, the plant is in the third
+])
+def test_clip_loss_with_a_nan_candidate_in_a_late_block(H, monkeypatch, mode, B, Bc, Fd, T, rows, off):
+    """The candidate set walked in row blocks (tests/test_clip_blocks_gpu.py, cases B and A), one NaN in a candidate of
+    the LAST block.  The reference: that candidate's norm and so its score column are NaN, the other columns stay
+    finite; every row's softmax holds a NaN, so the loss, all of dEst and all of dCand are NaN.
+
+    f16x2: ``share_amax`` hands every block the maximum of the whole candidate tensor.  The amax pass folds with
+    ``fmaxf``, which drops a NaN: the shared maximum is that of the FINITE elements (pinned below), the clean blocks are
+    scaled as if the plant were not there and the NaN travels through the operand split of its own block alone -- a NaN
+    maximum (scale 1, no scaling at all) would not have spoilt the other columns either, but it would have cost them
+    their f16 headroom."""
+    from brainmagick_amd import functional as BF
+    g = _gen(B + Bc)
+    K = Fd * T
+    est = torch.randn(B, Fd, T, generator=g) * 0.5
+    cand = torch.randn(Bc, Fd, T, generator=g) * 1.5 + 0.2
+    est += 0.02 * cand[off:off + B]
+    bad_row = Bc - 1
+    cand[bad_row, Fd // 2, 5] = NAN
+    finite_max = float(cand[torch.isfinite(cand)].abs().max())
+    e = est.double().requires_grad_(True)
+    c = cand.double().requires_grad_(True)
+    s = e.flatten(1) @ c.flatten(1).t() / (1e-8 + c.flatten(1).norm(dim=1))
+    ref_loss = F.cross_entropy(s, torch.arange(B) + off)
+    (ref_loss * 1.7).backward()
+    bad = ~torch.isfinite(s.detach())
+    assert bool(bad[:, bad_row].all()) and int(bad.sum()) == B and math.isnan(float(ref_loss))
+    assert bool(torch.isnan(e.grad).all()) and bool(torch.isnan(c.grad).all())
+    monkeypatch.setattr(BF, "_CLIP_BLOCK_BYTES", rows * K * 4)
+    blocks = BF._candidate_blocks(Bc, K)
+    assert len(blocks) > 2 and blocks[-1][0] <= bad_row and blocks[-2][0] + blocks[-2][1] <= bad_row
+    H.set_compute_dtype(mode)
+    try:
+        eg, cg = est.cuda().requires_grad_(True), cand.cuda().requires_grad_(True)
+        loss, scores = BF.ClipLossFn.apply(eg, cg, off)
+        (loss * 1.7).backward()
+        if mode == "f16x2":
+            assert float(H.amax(cg).max()) == finite_max
+        no_grad_scores = BF.clip_scores(eg.detach(), cg.detach())
+    finally:
+        H.set_compute_dtype(H.DEFAULT_COMPUTE_DTYPE)
+    for name, got in (("scores", scores), ("clip_scores", no_grad_scores)):
+        got = got.double().cpu()
+        assert torch.equal(~torch.isfinite(got), bad), f"{name}[{mode}]: non-finite elements differ from the reference's"
+        assert rel_l2(got[~bad], s.detach()[~bad]) < FWD_TOL
+    assert math.isnan(float(loss))
+    assert bool(torch.isnan(eg.grad).all()) and bool(torch.isnan(cg.grad).all())
+
+
 @pytest.mark.parametrize("kind", ["l1", "mse"])
 @pytest.mark.parametrize("T", [68, 67])
 def test_regress_loss(H, kind, T):
