@@ -1,4 +1,5 @@
-// Regression objective and its test metrics (bm/losses.py:11-26, bm/metrics.py:37-170).
+// Regression objective and its test metrics (bm/losses.py:11-26, bm/metrics.py:37-170); further down FeatureDecodingLoss
+// (bm/losses.py:117-173) and ClassificationAcc (bm/metrics.py:173-180) on the same helpers and workspace.
 //
 //   forward   loss = sum_{selected} w(e - o) / count       w = |.| (L1) or (.)^2 (MSE)
 //   backward  dEst = g * w'(e - o) * m / count, dOut = -dEst
@@ -19,14 +20,20 @@
 #define RG_MASK_FULL 2      // [B][F][T]
 #define RG_L1 0
 #define RG_MSE 1
+#define FD_MAX_FEATURES 16
+#define FD_MAX_K 16384
+#define FD_MAX_BLOCKS 2048
+#define FD_SLOTS (FD_MAX_FEATURES + 1)      // one (numerator, denominator) pair per feature + the selected positions
 
-// Workspace layout (bm_regress_workspace_bytes): two ticket counters (zero between launches: the last workgroup of a
-// launch resets its counter), the forward partials (sum, count) and the backward's partial maxima.
+// Workspace layout (bm_regress_workspace_bytes): three ticket counters (zero between launches: the last workgroup of a
+// launch resets its counter), the forward partials (sum, count), the backward's partial maxima and the per-feature
+// partials of the feature-decoding forward.
 struct RgWs {
-    unsigned* tickets;      // [0]: forward, [1]: backward
+    unsigned* tickets;      // [0]: forward, [1]: backward, [2]: feature-decoding forward
     double* part_sum;       // [RG_FWD_MAX_BLOCKS]
     double* part_cnt;       // [RG_FWD_MAX_BLOCKS]
     float* part_max;        // [RG_BWD_MAX_PARTIALS], [F][nsplit]
+    double* part_fd;        // [FD_SLOTS][2][FD_MAX_BLOCKS]
 };
 static RgWs rg_ws(void* base) {
     char* p = (char*)base;
@@ -35,9 +42,11 @@ static RgWs rg_ws(void* base) {
     w.part_sum = (double*)(p + 64);
     w.part_cnt = w.part_sum + RG_FWD_MAX_BLOCKS;
     w.part_max = (float*)(w.part_cnt + RG_FWD_MAX_BLOCKS);
+    w.part_fd = (double*)(w.part_max + RG_BWD_MAX_PARTIALS);
     return w;
 }
-static const long RG_WS_BYTES = 64 + 2L * RG_FWD_MAX_BLOCKS * 8 + RG_BWD_MAX_PARTIALS * 4L;
+static const long RG_WS_BYTES = 64 + 2L * RG_FWD_MAX_BLOCKS * 8 + RG_BWD_MAX_PARTIALS * 4L +
+                                2L * FD_SLOTS * FD_MAX_BLOCKS * 8;
 
 extern "C" long bm_regress_workspace_bytes(void) { return RG_WS_BYTES; }
 
@@ -272,7 +281,7 @@ extern "C" int bm_regress_loss_bwd(const float* est, const float* out, const uns
     nsplit = cdiv(B, bper);
     const bool vec = T % 4 == 0 && (((uintptr_t)est | (uintptr_t)out | (uintptr_t)d_est | (uintptr_t)d_out) & 15) == 0 &&
                      (mask_mode == RG_MASK_NONE || ((uintptr_t)mask & 3) == 0);
-    const RgWs ws = amax_out ? rg_ws(workspace) : RgWs{nullptr, nullptr, nullptr, nullptr};
+    const RgWs ws = amax_out ? rg_ws(workspace) : RgWs{nullptr, nullptr, nullptr, nullptr, nullptr};
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nsplit, F);
     if (vec)
@@ -348,4 +357,371 @@ extern "C" int bm_regress_metric_update(const float* est, long est_bstride, cons
     hipLaunchKernelGGL(regress_metric_kernel, dim3(cdiv(ncol, RG_THREADS)), dim3(RG_THREADS), 0, (hipStream_t)stream,
                        est, est_bstride, out, out_bstride, mask, mask_bstride, mask_full, B, F, T, t0, acc);
     return bm_check_launch("regress_metric_update");
+}
+
+// ---- FeatureDecodingLoss (bm/losses.py:117-173): MSE on the continuous features, weighted cross-entropy on the
+// categorical ones, all features in ONE forward and ONE backward launch ------------------------------------------------
+// A workgroup owns tiles of 64 consecutive positions (b, t) of the flat [B][T] axis; its four wavefronts share the
+// channels of a feature (wavefront w takes the channels w, w + 4, ...), so every load is 64 consecutive floats of one
+// channel row.  The feature loop is the outer one: a thread carries the numerator / denominator of one feature at a
+// time (no per-thread table).  A categorical feature's logits are read once: every wavefront keeps a running maximum
+// and an fp64 sum of exponentials over its share of the K classes, the four pairs are merged through LDS.
+#define FD_CONTINUOUS 0
+#define FD_CATEGORICAL 1
+#define FD_RANGE_BIT 4          // flag word: a category outside [0, K)  (the assert of bm/losses.py:150)
+#define FD_NO_MASK_BIT 2
+#define FD_TILE 64
+#define FD_UNROLL 8
+#define FD_BWD_MAX_TILES 16384
+struct FdFeature {
+    int kind, est_start, width, out_start, weight_off;
+};
+struct FdTable {
+    int n;
+    FdFeature f[FD_MAX_FEATURES];
+};
+
+struct FdPos {
+    unsigned idx, b, t;     // flat position (clamped into range), segment, sample
+    bool in, sel;           // inside [0, B T); selected by the mask
+};
+__device__ __forceinline__ FdPos fd_pos(unsigned tile, unsigned npos, unsigned T, const BmFastDiv& div_t,
+                                        const unsigned char* __restrict__ mask) {
+    FdPos p;
+    const unsigned i = tile * FD_TILE + (threadIdx.x & 63);
+    p.in = i < npos;
+    p.idx = p.in ? i : npos - 1;        // lanes past the end read the last position and count for nothing
+    p.b = bm_div(p.idx, div_t);
+    p.t = p.idx - p.b * T;
+    p.sel = p.in && (!mask || mask[p.idx] != 0);       // mask [B][1][T]: the flat position is its index
+    return p;
+}
+__device__ __forceinline__ double* fd_part(const RgWs& ws, int slot, int which) {
+    return ws.part_fd + ((size_t)slot * 2 + which) * FD_MAX_BLOCKS;
+}
+// the target class of a position: truncation towards zero like torch's .long(); valid inside [0, K)
+__device__ __forceinline__ bool fd_target(float tv, int K, int& y) {
+    const bool valid = tv > -1.f && tv < (float)K;      // false for NaN
+    y = valid ? (int)tv : 0;
+    return valid;
+}
+
+__global__ __launch_bounds__(RG_THREADS) void feature_decoding_fwd_kernel(
+    const float* __restrict__ est, const float* __restrict__ out, const unsigned char* __restrict__ mask,
+    const float* __restrict__ weights, FdTable tab, unsigned npos, unsigned ntiles, int C, int Co, unsigned T,
+    BmFastDiv div_t, RgWs ws, float* __restrict__ loss, float* __restrict__ terms, double* __restrict__ denoms,
+    float* __restrict__ lse, int* __restrict__ flag) {
+    __shared__ double sh[9 + 2 * RG_THREADS];
+    double* sh_s = sh + 9;
+    double* sh_m = sh_s + RG_THREADS;
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int bad = 0;
+    double cnt = 0.0;
+    if (wave == 0)
+        for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
+            cnt += fd_pos(tile, npos, T, div_t, mask).sel ? 1.0 : 0.0;
+    cnt = rg_block_sum(cnt, sh);
+    if (threadIdx.x == 0) rg_store_partial(fd_part(ws, FD_MAX_FEATURES, 0) + blockIdx.x, cnt);
+    int ci = 0;
+    for (int f = 0; f < tab.n; ++f) {
+        const FdFeature ft = tab.f[f];
+        double num = 0.0, den = 0.0;
+        if (ft.kind == FD_CONTINUOUS) {
+            for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+                const FdPos p = fd_pos(tile, npos, T, div_t, mask);
+                const float* e = est + ((size_t)p.b * C + ft.est_start) * T + p.t;
+                const float* o = out + ((size_t)p.b * Co + ft.out_start) * T + p.t;
+                double s = 0.0;
+                for (int c0 = wave; c0 < ft.width; c0 += 4 * FD_UNROLL) {
+                    float ev[FD_UNROLL], ov[FD_UNROLL];
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) {          // loads first: eight channel rows in flight
+                        const int c = c0 + 4 * i < ft.width ? c0 + 4 * i : c0;
+                        ev[i] = e[(size_t)c * T];
+                        ov[i] = o[(size_t)c * T];
+                    }
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) {
+                        const double d = (double)(ev[i] - ov[i]);  // the fp32 difference, as torch forms it
+                        s += c0 + 4 * i < ft.width ? d * d : 0.0;
+                    }
+                }
+                num += p.sel ? s : 0.0;
+            }
+        } else {
+            const int K = ft.width;
+            for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+                const FdPos p = fd_pos(tile, npos, T, div_t, mask);
+                const float* x = est + ((size_t)p.b * C + ft.est_start) * T + p.t;
+                // running maximum m and s = sum exp(x - m') with m' = m, or 0 while m is still -inf
+                float m = -INFINITY;
+                double s = 0.0;
+                for (int k0 = wave; k0 < K; k0 += 4 * FD_UNROLL) {
+                    float xv[FD_UNROLL];
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) xv[i] = x[(size_t)(k0 + 4 * i < K ? k0 + 4 * i : k0) * T];
+                    float cm = m;
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) cm = k0 + 4 * i < K ? fmaxf(cm, xv[i]) : cm;
+                    const float base = cm == -INFINITY ? 0.f : cm;
+                    s *= m == -INFINITY ? 1.0 : (double)expf(m - base);      // (no maximum yet: s is 0, or NaN)
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) s += k0 + 4 * i < K ? (double)expf(xv[i] - base) : 0.0;
+                    m = cm;
+                }
+                sh_m[threadIdx.x] = (double)m;
+                sh_s[threadIdx.x] = s;
+                __syncthreads();
+                if (wave == 0) {
+                    float mw[4];
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) mw[w] = (float)sh_m[w * 64 + lane];
+                    const float mx = fmaxf(fmaxf(mw[0], mw[1]), fmaxf(mw[2], mw[3]));
+                    const float base = mx == -INFINITY ? 0.f : mx;
+                    double S = 0.0;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w)
+                        S += sh_s[w * 64 + lane] * (mw[w] == -INFINITY ? 1.0 : (double)expf(mw[w] - base));
+                    const double l = (double)base + log(S);
+                    const float tv = out[((size_t)p.b * Co + ft.out_start) * T + p.t];
+                    int y;
+                    const bool valid = fd_target(tv, K, y);
+                    if (p.in && (tv >= (float)K || (p.sel && !valid))) bad = 1;
+                    const float xy = x[(size_t)y * T];
+                    const float w = ft.weight_off >= 0 ? weights[ft.weight_off + y] : 1.f;
+                    if (p.in) lse[(size_t)ci * npos + p.idx] = (float)l;
+                    const bool on = p.sel && valid;
+                    num += on ? (double)w * (l - (double)xy) : 0.0;
+                    den += on ? (double)w : 0.0;
+                }
+                __syncthreads();
+            }
+            ++ci;
+        }
+        num = rg_block_sum(num, sh);
+        den = rg_block_sum(den, sh + 4);
+        if (threadIdx.x == 0) {
+            rg_store_partial(fd_part(ws, f, 0) + blockIdx.x, num);
+            rg_store_partial(fd_part(ws, f, 1) + blockIdx.x, den);
+        }
+    }
+    const int any_bad = __syncthreads_or(bad);
+    if (any_bad && flag && threadIdx.x == 0) atomicOr(flag, FD_RANGE_BIT);
+    if (!rg_last_arriver(ws.tickets + 2, gridDim.x, sh + 8)) return;
+    // the last workgroup folds the partials in block order, feature by feature
+    double nsel = 0.0;
+    for (unsigned k = threadIdx.x; k < gridDim.x; k += RG_THREADS) nsel += fd_part(ws, FD_MAX_FEATURES, 0)[k];
+    nsel = rg_block_sum(nsel, sh);
+    float total = 0.f;
+    for (int f = 0; f < tab.n; ++f) {
+        double num = 0.0, den = 0.0;
+        for (unsigned k = threadIdx.x; k < gridDim.x; k += RG_THREADS) {
+            num += fd_part(ws, f, 0)[k];
+            den += fd_part(ws, f, 1)[k];
+        }
+        num = rg_block_sum(num, sh);
+        den = rg_block_sum(den, sh + 4);
+        if (tab.f[f].kind == FD_CONTINUOUS) den = nsel * (double)tab.f[f].width;
+        if (threadIdx.x == 0) {
+            const float term = (float)(num / den);    // nothing selected: 0 / 0 = NaN, like torch's mean of nothing
+            terms[f] = term;
+            denoms[f] = den;
+            total += term;                            // fp32, in feature order (the reference's `loss += ...`)
+        }
+    }
+    if (threadIdx.x == 0) {
+        *loss = total;
+        if (nsel == 0.0 && flag) atomicOr(flag, FD_NO_MASK_BIT);
+    }
+}
+
+// Every element of d_est is written exactly once (zero where the mask does not select): blockIdx.y splits the
+// channels of every feature further (wavefront w of slice s takes the channels 4 s + w, 4 (s + gridDim.y) + w, ...).
+__global__ __launch_bounds__(RG_THREADS) void feature_decoding_bwd_kernel(
+    const float* __restrict__ est, const float* __restrict__ out, const unsigned char* __restrict__ mask,
+    const float* __restrict__ weights, FdTable tab, unsigned npos, unsigned ntiles, int C, int Co, unsigned T,
+    BmFastDiv div_t, const float* __restrict__ grad_out, const double* __restrict__ denoms,
+    const float* __restrict__ lse, float* __restrict__ d_est) {
+    const int first = (int)(threadIdx.x >> 6) + 4 * (int)blockIdx.y, step = 4 * (int)gridDim.y;
+    const float g = *grad_out;
+    int ci = 0;
+    for (int f = 0; f < tab.n; ++f) {
+        const FdFeature ft = tab.f[f];
+        const double den = denoms[f];
+        if (ft.kind == FD_CONTINUOUS) {
+            const float scale = (float)(2.0 / den);        // torch: d * (2 / N) * g
+            for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+                const FdPos p = fd_pos(tile, npos, T, div_t, mask);
+                const size_t at = ((size_t)p.b * C + ft.est_start) * T + p.t;
+                const float* o = out + ((size_t)p.b * Co + ft.out_start) * T + p.t;
+                for (int c0 = first; c0 < ft.width; c0 += step * FD_UNROLL) {
+                    float ev[FD_UNROLL], ov[FD_UNROLL];
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) {
+                        const int c = c0 + step * i < ft.width ? c0 + step * i : c0;
+                        ev[i] = est[at + (size_t)c * T];
+                        ov[i] = o[(size_t)c * T];
+                    }
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) {
+                        const int c = c0 + step * i;
+                        if (c < ft.width && p.in) d_est[at + (size_t)c * T] = p.sel ? (ev[i] - ov[i]) * scale * g : 0.f;
+                    }
+                }
+            }
+        } else {
+            const int K = ft.width;
+            for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+                const FdPos p = fd_pos(tile, npos, T, div_t, mask);
+                const size_t at = ((size_t)p.b * C + ft.est_start) * T + p.t;
+                int y;
+                const bool on = fd_target(out[((size_t)p.b * Co + ft.out_start) * T + p.t], K, y) && p.sel;
+                const float w = ft.weight_off >= 0 ? weights[ft.weight_off + y] : 1.f;
+                const float coef = g * (float)((double)w / den);
+                const float l = lse[(size_t)ci * npos + p.idx];
+                for (int k0 = first; k0 < K; k0 += step * FD_UNROLL) {
+                    float xv[FD_UNROLL];
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i)
+                        xv[i] = est[at + (size_t)(k0 + step * i < K ? k0 + step * i : k0) * T];
+#pragma unroll
+                    for (int i = 0; i < FD_UNROLL; ++i) {
+                        const int k = k0 + step * i;
+                        const float v = coef * (expf(xv[i] - l) - (k == y ? 1.f : 0.f));
+                        if (k < K && p.in) d_est[at + (size_t)k * T] = on ? v : 0.f;
+                    }
+                }
+            }
+            ++ci;
+        }
+    }
+}
+
+// The launcher's copy of the caller's table [n][5] = {kind, est_start, width, out_start, weight_off}: the features
+// must tile the channels of est (continuous: width, categorical: K) and of out (continuous: width, categorical: 1)
+// in order -- that is what lets the backward write every element of d_est exactly once.
+static int fd_table(const char* what, const int* table, int n_features, int B, int C, int Co, int T, long n_weights,
+                    bool have_weights, FdTable& tab, int& n_cat, int& max_width) {
+    BM_REQUIRE(table && n_features >= 1 && n_features <= FD_MAX_FEATURES, "%s: 1 .. %d features, got %d", what,
+               FD_MAX_FEATURES, n_features);
+    BM_REQUIRE(B > 0 && C > 0 && Co > 0 && T > 0 && (long)B * C * T < (1L << 31) && (long)B * Co * T < (1L << 31),
+               "%s: bad shape (B C T must stay below 2^31)", what);
+    tab.n = n_features;
+    n_cat = 0;
+    max_width = 1;
+    int e = 0, o = 0;
+    for (int f = 0; f < n_features; ++f) {
+        FdFeature& ft = tab.f[f];
+        ft.kind = table[5 * f], ft.est_start = table[5 * f + 1], ft.width = table[5 * f + 2];
+        ft.out_start = table[5 * f + 3], ft.weight_off = table[5 * f + 4];
+        BM_REQUIRE(ft.kind == FD_CONTINUOUS || ft.kind == FD_CATEGORICAL, "%s: feature %d: kind %d", what, f, ft.kind);
+        BM_REQUIRE(ft.width >= 1 && ft.est_start == e && ft.out_start == o,
+                   "%s: feature %d does not follow its predecessor (est %d, expected %d; out %d, expected %d; width %d)",
+                   what, f, ft.est_start, e, ft.out_start, o, ft.width);
+        e += ft.width;
+        if (ft.kind == FD_CATEGORICAL) {
+            BM_REQUIRE(ft.width <= FD_MAX_K, "%s: feature %d: %d classes exceed %d", what, f, ft.width, FD_MAX_K);
+            BM_REQUIRE(ft.weight_off == -1 || (have_weights && ft.weight_off >= 0 &&
+                                               (long)ft.weight_off + ft.width <= n_weights),
+                       "%s: feature %d: weight offset %d outside the %ld weights", what, f, ft.weight_off, n_weights);
+            o += 1;
+            ++n_cat;
+        } else {
+            ft.weight_off = -1;
+            o += ft.width;
+        }
+        max_width = ft.width > max_width ? ft.width : max_width;
+    }
+    BM_REQUIRE(e == C && o == Co, "%s: the features span %d / %d channels, est has %d and out %d", what, e, o, C, Co);
+    return BM_OK;
+}
+
+extern "C" int bm_feature_decoding_fwd(const float* est, const float* out, const unsigned char* mask,
+                                       const float* weights, long n_weights, const int* table, int n_features, int B,
+                                       int C, int Co, int T, float* loss, float* terms, double* denoms, float* lse,
+                                       void* workspace, long workspace_bytes, int* flag, void* stream) {
+    FdTable tab;
+    int n_cat, max_width;
+    const int rc = fd_table("feature_decoding_fwd", table, n_features, B, C, Co, T, n_weights, weights != nullptr, tab,
+                            n_cat, max_width);
+    if (rc != BM_OK) return rc;
+    BM_REQUIRE(est && out && loss && terms && denoms && (lse || n_cat == 0), "feature_decoding_fwd: null pointer");
+    if (!workspace || workspace_bytes < RG_WS_BYTES)
+        return bm_set_error(BM_ERR_WORKSPACE, "feature_decoding_fwd: workspace");
+    const unsigned npos = (unsigned)((long)B * T);
+    const unsigned ntiles = (unsigned)cdiv(npos, FD_TILE);
+    const unsigned blocks = ntiles < FD_MAX_BLOCKS ? ntiles : FD_MAX_BLOCKS;
+    hipLaunchKernelGGL(feature_decoding_fwd_kernel, dim3(blocks), dim3(RG_THREADS), 0, (hipStream_t)stream, est, out,
+                       mask, weights, tab, npos, ntiles, C, Co, (unsigned)T, bm_fastdiv((unsigned)T), rg_ws(workspace),
+                       loss, terms, denoms, lse, flag);
+    return bm_check_launch("feature_decoding_fwd");
+}
+
+extern "C" int bm_feature_decoding_bwd(const float* est, const float* out, const unsigned char* mask,
+                                       const float* weights, long n_weights, const int* table, int n_features, int B,
+                                       int C, int Co, int T, const float* grad_out, const double* denoms,
+                                       const float* lse, float* d_est, void* stream) {
+    FdTable tab;
+    int n_cat, max_width;
+    const int rc = fd_table("feature_decoding_bwd", table, n_features, B, C, Co, T, n_weights, weights != nullptr, tab,
+                            n_cat, max_width);
+    if (rc != BM_OK) return rc;
+    BM_REQUIRE(est && out && grad_out && denoms && d_est && (lse || n_cat == 0), "feature_decoding_bwd: null pointer");
+    const unsigned npos = (unsigned)((long)B * T);
+    const unsigned ntiles = (unsigned)cdiv(npos, FD_TILE);
+    const unsigned gx = ntiles < FD_BWD_MAX_TILES ? ntiles : FD_BWD_MAX_TILES;
+    // ~2 048 workgroups: short batches split the channels of the widest feature over blockIdx.y
+    int gy = cdiv(2048, gx);
+    const int most = cdiv(max_width, 4);
+    gy = gy > most ? most : gy;
+    gy = gy > 64 ? 64 : gy;
+    hipLaunchKernelGGL(feature_decoding_bwd_kernel, dim3(gx, gy), dim3(RG_THREADS), 0, (hipStream_t)stream, est, out,
+                       mask, weights, tab, npos, ntiles, C, Co, (unsigned)T, bm_fastdiv((unsigned)T), grad_out, denoms,
+                       lse, d_est);
+    return bm_check_launch("feature_decoding_bwd");
+}
+
+// ---- ClassificationAcc (bm/metrics.py:173-180): one thread per (b, t) of the window [t0, T) ---------------------------
+// pred = the first index of the maximum over the K rows (a NaN counts as the maximum: torch.argmax); a selected position
+// adds 1 to count[t] and, when (float)pred == target, 1 to hits[t].  Integer atomics: the sums do not depend on the
+// order, two runs are equal.
+__global__ __launch_bounds__(RG_THREADS) void class_acc_kernel(const float* __restrict__ est, long est_bstride,
+                                                               const float* __restrict__ tgt, long tgt_bstride,
+                                                               const unsigned char* __restrict__ mask,
+                                                               long mask_bstride, int B, int K, int T, int t0,
+                                                               unsigned long long* __restrict__ acc) {
+    const int Tw = T - t0;
+    const long i = (long)blockIdx.x * RG_THREADS + threadIdx.x;
+    if (i >= (long)B * Tw) return;
+    const int b = (int)(i / Tw), col = (int)(i - (long)b * Tw), t = t0 + col;
+    if (mask && !mask[b * mask_bstride + t]) return;
+    const float* x = est + b * est_bstride + t;
+    float best = x[0];
+    int pred = 0;
+    for (int k0 = 1; k0 < K; k0 += FD_UNROLL) {
+        float xv[FD_UNROLL];
+#pragma unroll
+        for (int i2 = 0; i2 < FD_UNROLL; ++i2) xv[i2] = x[(long)(k0 + i2 < K ? k0 + i2 : k0) * T];
+#pragma unroll
+        for (int i2 = 0; i2 < FD_UNROLL; ++i2) {
+            const bool take = k0 + i2 < K && best == best && (xv[i2] > best || xv[i2] != xv[i2]);
+            best = take ? xv[i2] : best;
+            pred = take ? k0 + i2 : pred;
+        }
+    }
+    atomicAdd(acc + Tw + col, 1ull);
+    if ((float)pred == tgt[b * tgt_bstride + t]) atomicAdd(acc + col, 1ull);
+}
+
+extern "C" int bm_class_acc_update(const float* est, long est_bstride, const float* target, long target_bstride,
+                                   const unsigned char* mask, long mask_bstride, int B, int K, int T, int t0, long* acc,
+                                   void* stream) {
+    BM_REQUIRE(B >= 0 && K > 0 && T > 0 && t0 >= 0 && t0 < T && acc, "class_acc_update: bad arguments");
+    BM_REQUIRE(B == 0 || (est && target), "class_acc_update: null pointer");
+    BM_REQUIRE((long)B * (T - t0) < (1L << 31) * RG_THREADS, "class_acc_update: too many positions");
+    if (B == 0) return BM_OK;
+    hipLaunchKernelGGL(class_acc_kernel, dim3(cdiv((long)B * (T - t0), RG_THREADS)), dim3(RG_THREADS), 0,
+                       (hipStream_t)stream, est, est_bstride, target, target_bstride, mask, mask_bstride, B, K, T, t0,
+                       (unsigned long long*)acc);
+    return bm_check_launch("class_acc_update");
 }

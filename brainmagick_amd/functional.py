@@ -553,6 +553,34 @@ class MaskedRegressionFn(torch.autograd.Function):
         return (dest if ctx.needs_input_grad[0] else None), dout, None, None, None
 
 
+class FeatureDecodingFn(torch.autograd.Function):
+    """FeatureDecodingLoss.forward (bm/losses.py:117-173): MSE on the continuous features + weighted cross-entropy on the
+    categorical ones, one forward and one backward launch for all features (csrc/regress.hip).  ``table``: a tuple of
+    (kind, est_start, width, out_start, weight_off) rows (hip_ops.feature_decoding_fwd); ``weights``: the class weights
+    of all categorical features in one fp32 device vector, or None; ``mask``: bool [B, 1, T] or None = all true.  Returns
+    (loss, terms [n_features], denoms [n_features]); the per-feature denominators and the positions' logsumexp stay on
+    the device for the backward (no host sync).  The gradient goes to ``estimate`` only.  ``flag`` (int32 device
+    tensor, nullable) receives the "no mask!" and "category out of range" bits."""
+
+    @staticmethod
+    def forward(ctx, estimate, output, mask, table, weights=None, flag=None):
+        estimate, output = _c(estimate), _c(output)
+        mask = None if mask is None else _c(mask)
+        loss, terms, denoms, lse = H.feature_decoding_fwd(estimate, output, mask, table, weights, flag)
+        ctx.table = table
+        ctx.save_for_backward(estimate, output, mask, weights, denoms, lse)
+        ctx.mark_non_differentiable(terms, denoms)
+        return loss, terms, denoms
+
+    @staticmethod
+    def backward(ctx, dloss, _dterms, _ddenoms):
+        estimate, output, mask, weights, denoms, lse = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        dest = H.feature_decoding_bwd(estimate, output, mask, ctx.table, weights, _c(dloss), denoms, lse)
+        return dest, None, None, None, None, None
+
+
 def _lstm_layer_params(params, layer: int, dirs: int):
     """[(w_ih, w_hh, b_ih, b_hh)] per direction out of nn.LSTM's flat parameter order."""
     base = layer * dirs * 4

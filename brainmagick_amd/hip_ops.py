@@ -539,7 +539,8 @@ def index_error_flag(device) -> torch.Tensor:
         device = torch.device("cuda", torch.cuda.current_device())
     flag = _index_err.get(device)
     if flag is None:
-        # [index out of range, non-finite input, unsupported (not all-true) ClipLoss mask]
+        # [index out of range, non-finite input, loss mask bits: 1 = ClipLoss mask not all-true, NO_MASK_BIT,
+        # CATEGORY_RANGE_BIT]
         flag = torch.zeros(3, device=device, dtype=torch.int32)
         _index_err[device] = flag
     return flag
@@ -1009,6 +1010,98 @@ def regress_metric_update(est: torch.Tensor, out: torch.Tensor, mask: tp.Optiona
     check(lib().bm_regress_metric_update(_p(est), est.stride(0), _p(out), out.stride(0), _p(mask),
                                          mask[0].numel() if mask is not None else 0, int(mode == 2), B, F, T, t0,
                                          _p(acc), _stream()), "bm_regress_metric_update")
+    return acc
+
+
+# FeatureDecodingLoss / ClassificationAcc (csrc/regress.hip).  ``table``: one row per feature, (kind, est_start, width,
+# out_start, weight_off) with kind 0 = continuous, 1 = categorical (width = number of classes) and weight_off the
+# feature's offset into ``weights`` or -1.
+FEATURE_CONTINUOUS, FEATURE_CATEGORICAL = 0, 1
+CATEGORY_RANGE_BIT = 4     # flag word slot 2: a class outside [0, K) (the assert of bm/losses.py:150)
+
+
+def _feature_table(table):
+    flat = [int(v) for row in table for v in row]
+    if not table or len(flat) != 5 * len(table):
+        raise BmHipError("feature_decoding: table must hold rows (kind, est_start, width, out_start, weight_off)")
+    return (ctypes.c_int * len(flat))(*flat), len(table)
+
+
+def _feature_decoding_args(est, out, mask, weights, what):
+    _req(est, f"{what}.est")
+    _req(out, f"{what}.out")
+    if est.dim() != 3 or out.dim() != 3 or est.shape[0] != out.shape[0] or est.shape[2] != out.shape[2]:
+        raise BmHipError(f"{what}: est {tuple(est.shape)} / out {tuple(out.shape)} must be [B, C, T] and [B, Co, T]")
+    B, C, T = est.shape
+    if mask is not None:
+        _req(mask, f"{what}.mask", torch.bool)
+        if tuple(mask.shape) != (B, 1, T):
+            raise BmHipError(f"{what}: mask of shape {tuple(mask.shape)} is not [B, 1, T] for {tuple(est.shape)}")
+    _opt(weights, f"{what}.weights")
+    return B, C, out.shape[1], T
+
+
+def feature_decoding_fwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[torch.Tensor], table,
+                         weights: tp.Optional[torch.Tensor] = None, flag: tp.Optional[torch.Tensor] = None):
+    """(loss [] fp32, terms [n_features] fp32, denoms [n_features] fp64, lse [n_categorical, B, T] fp32) of
+    FeatureDecodingLoss, device side, no sync.  ``flag`` (int32 device tensor, nullable): element 0 gets NO_MASK_BIT when
+    nothing is selected (the loss is NaN) and CATEGORY_RANGE_BIT when a class is outside [0, K)."""
+    B, C, Co, T = _feature_decoding_args(est, out, mask, weights, "feature_decoding")
+    rows, n = _feature_table(table)
+    n_cat = sum(1 for row in table if row[0] == FEATURE_CATEGORICAL)
+    loss = torch.empty((), device=est.device, dtype=torch.float32)
+    terms = torch.empty(n, device=est.device, dtype=torch.float32)
+    denoms = torch.empty(n, device=est.device, dtype=torch.float64)
+    lse = torch.empty(n_cat, B, T, device=est.device, dtype=torch.float32)
+    ws = _regress_ws(est.device)
+    check(lib().bm_feature_decoding_fwd(_p(est), _p(out), _p(mask), _p(weights),
+                                        0 if weights is None else weights.numel(), rows, n, B, C, Co, T, _p(loss),
+                                        _p(terms), _p(denoms), _p(lse), _p(ws), ws.numel(),
+                                        _p(_opt(flag, "flag", torch.int32)), _stream()), "bm_feature_decoding_fwd")
+    return loss, terms, denoms, lse
+
+
+def feature_decoding_bwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[torch.Tensor], table,
+                         weights: tp.Optional[torch.Tensor], grad_out: torch.Tensor, denoms: torch.Tensor,
+                         lse: torch.Tensor) -> torch.Tensor:
+    """dEst of FeatureDecodingLoss: allocated with ``empty``, every element written by the one launch.  (The gradient's
+    maximum is not published: an f16x2 consumer finds it with the generic ``amax`` scan.)"""
+    B, C, Co, T = _feature_decoding_args(est, out, mask, weights, "feature_decoding_bwd")
+    rows, n = _feature_table(table)
+    dest = torch.empty_like(est)
+    check(lib().bm_feature_decoding_bwd(_p(est), _p(out), _p(mask), _p(weights),
+                                        0 if weights is None else weights.numel(), rows, n, B, C, Co, T,
+                                        _p(_req(grad_out, "grad_out")), _p(_req(denoms, "denoms", torch.float64)),
+                                        _p(_req(lse, "lse")), _p(dest), _stream()), "bm_feature_decoding_bwd")
+    return dest
+
+
+def class_acc_update(est: torch.Tensor, target: torch.Tensor, mask: tp.Optional[torch.Tensor], acc: torch.Tensor,
+                     t0: int = 0) -> torch.Tensor:
+    """acc [2, T - t0] int64 (hits, selected count) += over the batch of est [B, K, T] (logits) against target [B, 1, T]
+    (the class as a float), columns t >= t0 only; channel slices of contiguous tensors are read in place.  mask: bool
+    [B, 1, T] or None."""
+    for t, n in ((est, "est"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _req(t, f"class_acc_update.{n}")
+        if t.dtype != torch.float32:
+            raise BmHipError(f"class_acc_update.{n}: expected dtype torch.float32, got {t.dtype}")
+    if est.dim() != 3 or target.dim() != 3 or tuple(target.shape) != (est.shape[0], 1, est.shape[2]):
+        raise BmHipError(f"class_acc_update: est {tuple(est.shape)} / target {tuple(target.shape)}: [B, K, T] and "
+                         "[B, 1, T]")
+    B, K, T = est.shape
+    est = est if est.stride()[1:] == (T, 1) else est.contiguous()
+    target = target if target.stride(2) == 1 else target.contiguous()
+    if mask is not None:
+        if mask.dtype != torch.bool or tuple(mask.shape) != (B, 1, T):
+            raise BmHipError(f"class_acc_update: mask must be bool [B, 1, T], got {mask.dtype} {tuple(mask.shape)}")
+        mask = _req(mask if mask.is_contiguous() else mask.contiguous(), "class_acc_update.mask", torch.bool)
+    _req(acc, "class_acc_update.acc", torch.int64)
+    if not 0 <= t0 < T or tuple(acc.shape) != (2, T - t0):
+        raise BmHipError(f"class_acc_update: acc {tuple(acc.shape)} / t0 {t0} for {tuple(est.shape)}")
+    check(lib().bm_class_acc_update(_p(est), est.stride(0), _p(target), target.stride(0), _p(mask),
+                                    T if mask is not None else 0, B, K, T, t0, _p(acc), _stream()),
+          "bm_class_acc_update")
     return acc
 
 

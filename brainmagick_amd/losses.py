@@ -3,6 +3,8 @@ same constructor, ``forward`` / ``get_scores`` / ``get_probabilities`` / ``trim_
 reference's argument meaning and assertion behaviour; the contraction over K = F*T, the candidate
 norms, the row softmax / cross-entropy and the backward GEMM are libbmhip kernels.
 """
+import typing as tp
+
 import torch
 
 from . import functional as BF
@@ -163,9 +165,92 @@ class L2Loss(_MaskedLoss):
     kind = "mse"
 
 
-def create_loss(name: str, **clip_kw) -> torch.nn.Module:
-    """The loss factory of bm/solver.py:76-94 (`optim.loss`): 'l1', 'mse' or 'clip' (``clip_kw`` = the `clip:`
-    configuration block, plus ``dset_args``)."""
+class FeatureDecodingLoss(torch.nn.Module):
+    """bm/losses.py:117-173 (`optim.loss: regression_classification`): MSE on the continuous features of
+    ``used_features`` plus cross-entropy on the categorical ones, every term a mean over the positions ``mask`` selects,
+    summed in feature order -- one forward and one backward kernel launch for the whole loss (csrc/regress.hip), no
+    gather, no transpose, no read-back.
+
+    ``used_features`` is what the reference hands over (bm.features.FeaturesBuilder), duck-typed: ``.values()``,
+    ``.get_slice(name, model_output=...)``, ``.dimension``, ``.output_dimension``; every feature has ``.name``,
+    ``.categorical``, ``.dimension``, ``.output_dimension``.  ``scaler``: None (unweighted; `optim.use_weighting` off),
+    a ``norm.DeviceBatchScaler`` or anything else with ``get_categorical_feature_weights(name)``; the class weights are
+    fetched once and kept on the device in one vector.
+
+    ``mask``: bool [B, 1, T] (the only shape the reference's categorical branch can index with) or None = all true (an
+    extension, as for L1Loss / L2Loss).  A class is the target channel truncated towards zero (``.long()``); -100
+    (torch's ignore_index) has NO special meaning here -- the reference's features never produce it -- and is out of
+    range like any other negative class.  The reference's two synchronising asserts (``mask.any()``, losses.py:133, and
+    "categories up to", losses.py:150) become bits of ``no_mask_flag`` (an int32 device word, set by the Solver): a
+    position with an out-of-range class contributes nothing, an empty mask gives NaN.  ``last_terms``: the per-feature
+    terms of the last call, a device tensor (no sync).  The gradient goes to the estimate only."""
+
+    def __init__(self, used_features, scaler):
+        super().__init__()
+        self.used_features = used_features
+        self.scaler = scaler
+        self.no_mask_flag = None    # Solver: the flag word slot that receives NO_MASK_BIT / CATEGORY_RANGE_BIT
+        self.last_terms: tp.Optional[torch.Tensor] = None
+        self._table = None
+        self._weights: tp.Dict[torch.device, tp.Optional[torch.Tensor]] = {}
+
+    def _plan(self):
+        """((kind, est_start, width, out_start, weight_off) per feature, host weights | None), built once."""
+        if self._table is None:
+            from . import hip_ops as H
+            rows, weights, n_weights = [], [], 0
+            for feature in self.used_features.values():
+                name = feature.name
+                sl = self.used_features.get_slice(name)
+                sl_out = self.used_features.get_slice(name, model_output=True)
+                if feature.categorical:
+                    assert sl.stop - sl.start == 1, \
+                        "Supporting only single categorical cross entropy for now."
+                    off = -1
+                    if self.scaler:
+                        w = self.scaler.get_categorical_feature_weights(name).detach().float().cpu().flatten()
+                        if w.numel() != sl_out.stop - sl_out.start:
+                            raise ValueError(f"feature {name}: {w.numel()} class weights for "
+                                             f"{sl_out.stop - sl_out.start} classes")
+                        off = n_weights
+                        weights.append(w)
+                        n_weights += w.numel()
+                    rows.append((H.FEATURE_CATEGORICAL, sl_out.start, sl_out.stop - sl_out.start, sl.start, off))
+                else:
+                    assert sl_out.stop - sl_out.start == sl.stop - sl.start, name
+                    rows.append((H.FEATURE_CONTINUOUS, sl_out.start, sl.stop - sl.start, sl.start, -1))
+            self._table = tuple(rows), (torch.cat(weights) if weights else None)
+        return self._table
+
+    def forward(self, estimate, output, mask=None):
+        assert estimate.shape[1] == self.used_features.output_dimension and \
+               output.shape[1] == self.used_features.dimension, \
+               "Invalid features dim received. Are you using the correct " \
+               "features for the loss?"
+        if mask is not None:
+            if mask.dtype != torch.bool:
+                raise TypeError(f"mask must be a bool tensor (the reference indexes with it), got {mask.dtype}")
+            if tuple(mask.shape) != (estimate.shape[0], 1, estimate.shape[-1]):
+                raise ValueError(f"mask must be [B, 1, T] = {(estimate.shape[0], 1, estimate.shape[-1])} (what the "
+                                 f"reference's categorical branch can index with), got {tuple(mask.shape)}")
+        if output.requires_grad:
+            raise NotImplementedError("FeatureDecodingLoss sends no gradient to the targets (a learnable feature model "
+                                      "is not supported with it)")
+        if not (estimate.is_cuda and output.is_cuda):
+            raise RuntimeError("brainmagick_amd.FeatureDecodingLoss runs on the MI355X HIP path only (no CPU fallback)")
+        table, host_weights = self._plan()
+        if estimate.device not in self._weights:
+            self._weights[estimate.device] = None if host_weights is None else host_weights.to(estimate.device)
+        loss, terms, _ = BF.FeatureDecodingFn.apply(estimate, output, mask, table, self._weights[estimate.device],
+                                                    self.no_mask_flag)
+        self.last_terms = terms
+        return loss
+
+
+def create_loss(name: str, used_features=None, scaler=None, **clip_kw) -> torch.nn.Module:
+    """The loss factory of bm/solver.py:76-94 (`optim.loss`): 'l1', 'mse', 'clip' (``clip_kw`` = the `clip:`
+    configuration block, plus ``dset_args``) or 'regression_classification' (``used_features`` = the features builder,
+    ``scaler`` = the fitted scaler when `optim.use_weighting`, else None)."""
     if name == "l1":
         return L1Loss()
     if name == "mse":
@@ -176,6 +261,8 @@ def create_loss(name: str, **clip_kw) -> torch.nn.Module:
         kw.pop("sync_grad", None)
         return ClipLoss(**kw)
     if name == "regression_classification":
-        raise NotImplementedError("optim.loss='regression_classification' (FeatureDecodingLoss, categorical features) "
-                                  "is not part of brainmagick_amd")
+        if used_features is None:
+            raise NotImplementedError("optim.loss='regression_classification' (FeatureDecodingLoss) needs the features "
+                                      "builder: create_loss(name, used_features=..., scaler=...)")
+        return FeatureDecodingLoss(used_features, scaler)
     raise ValueError(f"Unsupported loss {name}")

@@ -1,5 +1,6 @@
-"""Test metrics of a regression model: mirror of ``bm/metrics.py`` (``OnlineCorrelation``, ``L1Reg``, ``L2Reg``) and of the
-non-categorical branch of ``bm/play.py:get_test_metrics`` / ``bm/solver.py:get_metric_constructors``.
+"""Test metrics of a decoding model: mirror of ``bm/metrics.py`` (``OnlineCorrelation``, ``L1Reg``, ``L2Reg``,
+``ClassificationAcc``) and of ``bm/play.py:get_test_metrics`` / the decode branch of
+``bm/solver.py:get_metric_constructors``.
 
 Same API as the reference (``get_constructor``, ``update(left, right, mask)``, ``get()``, ``reduce(stats)``, the
 slices and the names).  ``update`` is ONE pass of the HIP kernel ``bm_regress_metric_update`` over the batch: the
@@ -79,11 +80,11 @@ class _ColumnSums(TestMetric):
         return self._acc
 
 
-def update_all(metrics: tp.Sequence[_ColumnSums], left: torch.Tensor, right: torch.Tensor,
+def update_all(metrics: tp.Sequence[TestMetric], left: torch.Tensor, right: torch.Tensor,
                mask: tp.Optional[torch.Tensor], t0: int = 0) -> None:
     """``metric.update(left, right, mask)`` for every metric, with ONE kernel pass per distinct pair of slices: metrics
     with the same slices that are always updated together share their accumulator (an L2Reg and an OnlineCorrelation of
-    one feature)."""
+    one feature).  A ``ClassificationAcc`` in the list takes its own pass."""
     for t, what in ((left, "left"), (right, "right")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"brainmagick_amd metrics run on the MI355X HIP path only (no CPU fallback): {what} is "
@@ -94,6 +95,9 @@ def update_all(metrics: tp.Sequence[_ColumnSums], left: torch.Tensor, right: tor
         raise TypeError(f"mask must be a bool tensor, got {mask.dtype}")
     groups: tp.Dict[tp.Any, tp.List[_ColumnSums]] = {}
     for m in metrics:
+        if isinstance(m, ClassificationAcc):
+            m._count_batch(left, right, mask, t0)
+            continue
         key = (m.left_slice.start, m.left_slice.stop, m.left_slice.step,
                m.right_slice.start, m.right_slice.stop, m.right_slice.step)
         groups.setdefault(key, []).append(m)
@@ -180,6 +184,63 @@ class L2Reg(AccumulativeMetric):
     @classmethod
     def reduce(cls, stats: tp.List[torch.Tensor]) -> float:
         return torch.stack(stats).mean().sqrt().item()
+
+
+class ClassificationAcc(TestMetric):
+    """bm/metrics.py:173-180: the share of selected positions whose arg-max over the class logits ``left[:, left_slice]``
+    equals the class in ``right[:, right_slice]`` (one channel), per time sample over the batch.  ``update`` is one pass
+    of the HIP kernel ``bm_class_acc_update`` into int64 [2, T - t0] counts (hits, selected) on the device."""
+
+    def __init__(self, left_slice: slice, right_slice: slice, name: str = "N/A", dim: int = 0):
+        super().__init__(left_slice, right_slice, name)
+        if dim != 0:
+            raise NotImplementedError("brainmagick_amd metrics accumulate over the batch dimension (dim=0) only")
+        self.dim = dim
+        self._acc: tp.Optional[torch.Tensor] = None
+
+    def _count_batch(self, left, right, mask, t0):
+        for t, what in ((left, "left"), (right, "right")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"brainmagick_amd metrics run on the MI355X HIP path only (no CPU fallback): {what} "
+                                   f"is on {t.device if isinstance(t, torch.Tensor) else type(t)}")
+        logits, target = left[:, self.left_slice], right[:, self.right_slice]
+        if self._acc is None:
+            self._acc = torch.zeros(2, logits.shape[2] - t0, device=logits.device, dtype=torch.int64)
+        H.class_acc_update(logits, target, mask, self._acc, t0)
+
+    def update(self, left: torch.Tensor, right: torch.Tensor, mask: tp.Optional[torch.Tensor],
+               t0: int = 0) -> "ClassificationAcc":
+        """``left``: fp32 [B, C, T] logits, ``right``: fp32 [B, C', T] with the class as a float, on the GPU; ``mask``:
+        bool [B, 1, T] (None: all true).  ``t0`` (extension): only the samples t >= t0 count."""
+        self._count_batch(left, right, mask, t0)
+        return self
+
+    def get(self) -> torch.Tensor:
+        """AccumulativeMetric.get (bm/metrics.py:147-153): fp64 [1, T'] hits / count, or tensor([0.]) when nothing was
+        counted."""
+        if self._acc is None or self._acc[1].sum() == 0:
+            return torch.Tensor([0.])
+        ret = (self._acc[0].double() / self._acc[1].double())[None]
+        assert not torch.isnan(ret).any(), "Tensor contain nans. Perhaps division by " \
+                                           f"zero cause that? {ret}"
+        return ret
+
+
+def metric_constructors(used_features) -> tp.List[tp.Callable[..., TestMetric]]:
+    """bm/solver.py:410-432, the decode task: per feature of ``used_features`` (the features builder, duck-typed as for
+    ``losses.FeatureDecodingLoss``) ``ClassificationAcc("acc_<name>")`` if it is categorical, else ``L2Reg("l2_<name>")``
+    and ``OnlineCorrelation("corr_<name>")``, with the reference's argument order (the L2 metric takes the feature slice
+    first)."""
+    ctors: tp.List[tp.Callable[..., TestMetric]] = []
+    for feature in used_features.values():
+        name = feature.name
+        feature_slice = used_features.get_slice(name)
+        model_out_slice = used_features.get_slice(name, model_output=True)
+        if feature.categorical:
+            ctors.append(ClassificationAcc.get_constructor(model_out_slice, feature_slice, name=f"acc_{name}"))
+        else:
+            ctors += regression_metric_constructors(name, feature_slice, model_out_slice)
+    return ctors
 
 
 def regression_metric_constructors(feature_name: str, feature_slice: slice = slice(None),

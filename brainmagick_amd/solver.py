@@ -1,6 +1,7 @@
 """Host-side mirror of the hot loop of ``bm/solver.py``: ``_process_batch`` (bm/solver.py:230-321)
 and the per-batch body of ``_run_one_epoch`` (bm/solver.py:343-390), for the decode task with the
-CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80).
+CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80) or
+FeatureDecodingLoss (bm/solver.py:81-86).
 Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
 construction) stays the reference's business.
 
@@ -17,12 +18,12 @@ import torch
 
 from . import distrib
 from . import hip_ops as H
-from .losses import ClipLoss, _MaskedLoss
+from .losses import ClipLoss, FeatureDecodingLoss, _MaskedLoss
 from .optim import FlatAdam
 
 
 class Solver:
-    def __init__(self, model: torch.nn.Module, loss: tp.Optional[tp.Union[ClipLoss, _MaskedLoss]] = None,
+    def __init__(self, model: torch.nn.Module, loss: tp.Optional[tp.Union[ClipLoss, _MaskedLoss, FeatureDecodingLoss]] = None,
                  optimizer: tp.Optional[FlatAdam] = None, device: str = "cuda",
                  offset_meg_ms: float = 0., sample_rate: float = 120., negatives: str = "local",
                  lr: float = 3e-4, betas=(0.9, 0.999), scale_reject=None,
@@ -34,13 +35,14 @@ class Solver:
         candidate all-gather.  Without it the block is the local batch's length and is verified over the ranks each
         step (one tiny all-reduce + read-back; that mode reads back its rejection count anyway).
 
-        ``loss``: ``ClipLoss()`` (default), ``L1Loss()`` or ``L2Loss()`` (`optim.loss`, ``losses.create_loss``).
+        ``loss``: ``ClipLoss()`` (default), ``L1Loss()``, ``L2Loss()`` or ``FeatureDecodingLoss(...)`` (`optim.loss`,
+        ``losses.create_loss``); the last three are "the regression losses" below.
         ``mask_loss`` (`task.mask_loss`, bm/solver.py:251-253) applies to the regression losses: False hands them
         ``mask=None`` (all true, what the reference's ``torch.ones_like`` means, without the tensor), True the batch's
         ``features_mask`` after the offset slice.  ClipLoss keeps receiving the batch's mask (it asserts it is all
         true)."""
         assert negatives in ("local", "node")
-        self.regression = isinstance(loss, _MaskedLoss)
+        self.regression = isinstance(loss, (_MaskedLoss, FeatureDecodingLoss))
         if self.regression:
             if n_negatives is not None:          # bm/solver.py:362: `assert self.args.optim.loss == 'clip'`
                 raise ValueError("n_negatives (bm optim.negatives) completes the CLIP candidates; it does not apply to "
@@ -48,6 +50,9 @@ class Solver:
             if negatives == "node":
                 raise ValueError(f'negatives="node" gathers CLIP candidates; {type(loss).__name__} has none: use '
                                  'negatives="local"')
+        if isinstance(loss, FeatureDecodingLoss) and feature_model is not None:
+            raise ValueError("FeatureDecodingLoss sends no gradient to its targets (one of them is a class index): it "
+                             "does not combine with a learnable feature_model")
         self.mask_loss = mask_loss
         self.batch_size = batch_size
         self.device = torch.device(device)
@@ -239,8 +244,8 @@ class Solver:
         return buf, event
 
     def _check_flags(self, ticket=None):
-        """The host's look at the device-side flag word: "non-finite input" (bm/solver.py:258-260), "ClipLoss mask not
-        all-true" (bm/losses.py:110) and "subject / layout index out of range" (the reference's `weights.gather` would
+        """The host's look at the device-side flag word: "non-finite input" (bm/solver.py:258-260), "no mask!", "category
+        out of range" (FeatureDecodingLoss, bm/losses.py:150), "ClipLoss mask not all-true" (bm/losses.py:110) and "subject / layout index out of range" (the reference's `weights.gather` would
         have raised, bm/models/common.py:57) -- the last two raised by the PREVIOUS step (``check_pending_flags()`` reads
         them without waiting for a next one).  With a ``ticket`` (``_post_flags``) only that earlier copy is waited
         for; without one this is a blocking read (evaluation, direct ``_process_batch`` callers)."""
@@ -259,6 +264,10 @@ class Solver:
         if bad_mask & H.NO_MASK_BIT:
             flag[2:3].zero_()
             raise AssertionError("no mask! (bm/solver.py:354-356: the loss mask selects no element)")
+        if bad_mask & H.CATEGORY_RANGE_BIT:
+            flag[2:3].zero_()
+            raise AssertionError("feature output_dim is too small for the categories the output contains, or a "
+                                 "selected category is negative / NaN (bm/losses.py:150)")
         if bad_mask:
             flag[2:3].zero_()
             raise AssertionError("mask is not supported for now (bm/losses.py:110; reported one step late)")

@@ -357,6 +357,41 @@ int bm_regress_metric_update(const float* est, long est_bstride, const float* ou
                              const unsigned char* mask, long mask_bstride, int mask_full, int B, int F, int T, int t0,
                              double* acc, void* stream);
 
+/* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip)  bm/losses.py:117-173, bm/metrics.py:173-180 ----
+ * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
+ * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
+ * (width channels of est and of out, MSE over the selected positions and those channels), 1 = categorical (width = K
+ * logits in est, ONE channel of out holding the class as a float, truncated towards zero like .long(); cross-entropy
+ * weighted by weights[weight_off + class], weight_off = -1: unweighted).  The rows must tile est's and out's channels in
+ * order; at most 16 features, K <= 16384, B C T < 2^31 -- anything else is BM_ERR_ARG.
+ * Forward (ONE launch): terms[f] = numerator / denoms[f] per feature (continuous: sum (e - o)^2 / (n_selected width);
+ * categorical: sum w_y (logsumexp(x) - x_y) / sum w_y, torch's weighted mean), *loss = their fp32 sum in feature
+ * order, lse [n_categorical][B][T] = the logsumexp of every position (saved for the backward).  One pass over the K
+ * logits (running maximum and sum), fp64 sums, workgroup partials folded in a fixed order by the workgroup that finishes
+ * last (workspace: bm_regress_workspace_bytes, as for bm_regress_loss_fwd).  Unselected positions are dropped by
+ * select.  flag (nullable, the Solver's flag word slot 2): bit 2 when nothing is selected (the loss is NaN; the
+ * reference's `assert mask.any()`, bm/losses.py:133), bit 4 when ANY position holds a class >= K or a selected one a
+ * negative or NaN class (bm/losses.py:150; torch would raise) -- such a position contributes nothing.  -100 has no
+ * special meaning (the reference's features never produce torch's ignore_index). */
+int bm_feature_decoding_fwd(const float* est, const float* out, const unsigned char* mask, const float* weights,
+                            long n_weights, const int* table, int n_features, int B, int C, int Co, int T, float* loss,
+                            float* terms, double* denoms, float* lse, void* workspace, long workspace_bytes, int* flag,
+                            void* stream);
+/* Backward (ONE launch): d_est = g 2 (e - o) / denoms[f] on continuous channels, g (w_y / denoms[f]) (softmax(x)_k -
+ * [k = y]) on categorical ones, exactly 0 at unselected (or out-of-range) positions; EVERY element of d_est is
+ * written once (no fill pass needed).  g = *grad_out, denoms and lse are read on the device. */
+int bm_feature_decoding_bwd(const float* est, const float* out, const unsigned char* mask, const float* weights,
+                            long n_weights, const int* table, int n_features, int B, int C, int Co, int T,
+                            const float* grad_out, const double* denoms, const float* lse, float* d_est, void* stream);
+/* ClassificationAcc.update, bm/metrics.py:173-180 with dim = 0: est [B][K][T] (rows T floats apart), target = ONE
+ * channel [B][T], mask bytes [B][1][T] or null; segments est_bstride / target_bstride floats and mask_bstride bytes
+ * apart.  acc = int64 [2][T - t0]: hits and selected count per column t >= t0 (trim_offset, bm/play.py:144-147),
+ * accumulated in place.  Prediction = first index of the maximum (NaN counts as the maximum: torch.argmax); a hit is
+ * (float)prediction == target. */
+int bm_class_acc_update(const float* est, long est_bstride, const float* target, long target_bstride,
+                        const unsigned char* mask, long mask_bstride, int B, int K, int T, int t0, long* acc,
+                        void* stream);
+
 /* Gradient of ClipLoss w.r.t. the candidates (learnable feature model, bm/solver.py:304-320):
  * coef[o] = alpha * (sum_b dscaled[b,o]*scores[b,o]) / |cand_o| ;  y[r] -= coef[r] * x[r]. */
 int bm_clip_cand_coef(const float* dscaled, const float* scores, const float* inv_norm,
