@@ -15,19 +15,7 @@
 // The reduction domain is a flat list of (segment, 32-sample time chunk) pairs; `nsplit` workgroups
 // share one output tile (split-K) and write separate partial tiles that pack.hip's
 // bm_reduce_splits folds in a fixed order (deterministic).
-#include "mfma_split.h"
-
-#define BKT 32
-
-struct GemmNTArgs {
-    const float* a; long a_sstride; long a_rstride;   // A[s][m][t]
-    const float* x; long x_sstride; long x_rstride;   // X[s][c][t]
-    const int* order;                                  // segment list (grouped) or null = identity
-    const int* seg;                                    // [G+1] group boundaries or null = one group [0, S)
-    float* part;                                       // [G*nsplit][M][Cn*KS]
-    int S, M, Cn, T, dil, nsplit, G;
-    int tiles_m, tiles_c;
-};
+#include "gemm_nt_common.h"
 
 // XWP = padded width of the staged X window (32 + 2*halo <= XWP), compile time so that the staging
 // registers can be a fixed-size vector.  The window is centred: it starts HP = (XWP-32)/2 samples
@@ -61,31 +49,12 @@ __global__ __launch_bounds__(WM * WC * 64) void gemm_nt_kernel(GemmNTArgs a) {
     float* As = smem;                          // [BM][PA]
     float* Xs = smem + BM * PA;                // [BC][PX]
 
-    // block -> (tile_m, tile_c, split, g).  XCD-aware: all tiles of one (g, split) -- which stream
-    // the SAME segments -- get consecutive logical ids, i.e. run on one XCD and share its L2.
-    int id = bm_xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = id % a.tiles_m; id /= a.tiles_m;
-    const int tc = id % a.tiles_c; id /= a.tiles_c;
-    const int split = id % a.nsplit;
-    const int g = id / a.nsplit;
-    const int m0 = tm * BM, c0 = tc * BC;
-
-    const int s_begin = a.seg ? a.seg[g] : 0;
-    const int s_end = a.seg ? a.seg[g + 1] : a.S;
-    const int cps = (a.T + BKT - 1) / BKT;                     // chunks per segment
-    const long nchunks = (long)(s_end - s_begin) * cps;
-    const long q_begin = nchunks * split / a.nsplit;
-    const long q_end = nchunks * (split + 1) / a.nsplit;
+    const GemmNTWork w = gemm_nt_work<BM, BC>(a);
+    const int m0 = w.m0, c0 = w.c0, s_begin = w.s_begin, cps = w.cps;
+    const long q_begin = w.q_begin, q_end = w.q_end;
 
     f32x16 acc[MT][NT][KS];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-#pragma unroll
-            for (int j = 0; j < KS; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][k][j][r] = 0.f;
+    gemm_nt_zero(acc);
 
     avec_t areg;
     xvec_t xreg;
@@ -204,45 +173,18 @@ __global__ __launch_bounds__(WM * WC * 64) void gemm_nt_kernel(GemmNTArgs a) {
 #undef NT_LOAD
 #undef NT_STORE
 
-    // epilogue: part[(g*nsplit+split)][m][c*KS + j]
-    const long N = (long)a.Cn * KS;
-    float* dst = a.part + (long)(g * a.nsplit + split) * a.M * N;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            const int c = c0 + wc * NT * 32 + k * 32 + nl;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < a.M && c < a.Cn) {
-#pragma unroll
-                    for (int j = 0; j < KS; ++j) dst[(long)m * N + (long)c * KS + j] = acc[i][k][j][r];
-                }
-            }
-        }
+    gemm_nt_store_partial<WM, WC, MT, NT, KS>(a, w, acc);
 }
 
 template <int WM, int WC, int MT, int NT, int KS, int XWP, bool VEC>
-static int launch_gemm_nt_v(GemmNTArgs a, hipStream_t stream) {
+static int launch_gemm_nt_v(const GemmNTArgs& a, hipStream_t stream) {
     constexpr int BM = WM * MT * 32, BC = WC * NT * 32;
-    const size_t lds = (size_t)(BM * (BKT + 1) + BC * (XWP + 1)) * sizeof(float);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<WM, WC, MT, NT, KS, XWP, VEC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return bm_set_error((int)e, "gemm_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_c = cdiv(a.Cn, BC);
-    const long nblocks = (long)a.tiles_m * a.tiles_c * a.nsplit * a.G;
-    if (nblocks <= 0) return BM_OK;
-    hipLaunchKernelGGL((gemm_nt_kernel<WM, WC, MT, NT, KS, XWP, VEC>), dim3((unsigned)nblocks),
-                       dim3(WM * WC * 64), lds, stream, a);
-    return bm_check_launch("gemm_nt");
+    return gemm_nt_launch(gemm_nt_kernel<WM, WC, MT, NT, KS, XWP, VEC>, a, BM, BC, WM * WC * 64,
+                          (size_t)(BM * (BKT + 1) + BC * (XWP + 1)) * sizeof(float), "gemm_nt", stream);
 }
 
 template <int WM, int WC, int MT, int NT, int KS, int XWP>
-static int launch_gemm_nt_w(GemmNTArgs a, hipStream_t stream) {
+static int launch_gemm_nt_w(const GemmNTArgs& a, hipStream_t stream) {
     // dwordx4 staging needs every row start 16-byte aligned and T a multiple of 4
     const bool vec = (a.T % 4 == 0) && (a.a_rstride % 4 == 0) && (a.x_rstride % 4 == 0) &&
                      (a.a_sstride % 4 == 0) && (a.x_sstride % 4 == 0) &&
@@ -251,27 +193,36 @@ static int launch_gemm_nt_w(GemmNTArgs a, hipStream_t stream) {
     return launch_gemm_nt_v<WM, WC, MT, NT, KS, XWP, false>(a, stream);
 }
 
-template <int WM, int WC, int MT, int NT, int KS>
-static int launch_gemm_nt(GemmNTArgs a, hipStream_t stream) {
-    const int halo = (KS >> 1) * a.dil;
-    if (KS == 1) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 32>(a, stream);
-    if (halo <= 16) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 64>(a, stream);
-    if (halo <= 32) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 96>(a, stream);
-    return bm_set_error(BM_ERR_UNSUPPORTED, "gemm_nt: (kernel_size/2)*dilation = %d exceeds the 32-sample halo", halo);
-}
+struct GemmNTF32 {
+    static constexpr const char* name = "gemm_nt";
+    template <int WM, int WC, int MT, int NT, int KS>
+    static int launch(const GemmNTArgs& a, hipStream_t stream) {
+        const int halo = (KS >> 1) * a.dil;
+        if (KS == 1) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 32>(a, stream);
+        if (halo <= 16) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 64>(a, stream);
+        if (halo <= 32) return launch_gemm_nt_w<WM, WC, MT, NT, KS, 96>(a, stream);
+        return bm_set_error(BM_ERR_UNSUPPORTED, "gemm_nt: (kernel_size/2)*dilation = %d exceeds the 32-sample halo", halo);
+    }
+};
 
-// Suggested split count so that the launch has ~>= 4 workgroups per CU.
+// Suggested split count.  One group: so that the launch has ~>= 4 workgroups per CU, >= 8 chunks of work each.
+// Grouped (per-subject / per-layout weight gradients): each group's (segment, chunk) list is split until ~512
+// workgroups exist, at most 8 ways, >= 8 chunks per split -- counted in 160 x 128 tiles, the tiles of kernels that
+// no longer exist (the narrow tiles are at most 128 x 128).  The constants stay as they are: the split count fixes
+// the summation order of the grouped gradients, and with it their bits.
 extern "C" int bm_gemm_nt_suggest_splits(int M, int Cn, int KS, int S, int T, int G) {
-    int tiles;
-    if (KS == 1) tiles = cdiv(M, prefer_big(M) ? 128 : 64) * cdiv(Cn, prefer_big(Cn) ? 128 : 64);
-    else tiles = cdiv(M, prefer_big(M) ? 128 : 64) * cdiv(Cn, 64);
-    long chunks = (long)S * cdiv(T, BKT);
-    if (G > 1) return 1;
-    long want = (1024 + tiles - 1) / tiles;
+    long want, chunks;
+    if (G > 1) {
+        const int tiles = cdiv(M, 160) * cdiv(Cn, 128) * G;
+        chunks = (long)(S / G > 0 ? S / G : 1) * cdiv(T, BKT);
+        want = 512 / tiles < 8 ? 512 / tiles : 8;
+    } else {
+        const int tiles = cdiv(M, prefer_big(M) ? 128 : 64) * cdiv(Cn, KS == 1 && prefer_big(Cn) ? 128 : 64);
+        chunks = (long)S * cdiv(T, BKT);
+        want = (1024 + tiles - 1) / tiles < 256 ? (1024 + tiles - 1) / tiles : 256;
+    }
     if (want > chunks / 8) want = chunks / 8;     // keep >= 8 chunks of work per workgroup
-    if (want < 1) want = 1;
-    if (want > 256) want = 256;
-    return (int)want;
+    return (int)(want < 1 ? 1 : want);
 }
 
 // Split count of the ClipLoss score contraction (M x Cn outputs, K = S * T long): one workgroup per CU -- more
@@ -289,27 +240,9 @@ extern "C" int bm_gemm_nt(const float* a, long a_sstride, long a_rstride, const 
                           long x_sstride, long x_rstride, const int* order, const int* seg,
                           float* part, int S, int G, int M, int Cn, int T, int KS, int dil,
                           int nsplit, void* stream) {
-    BM_REQUIRE(a && x && part, "gemm_nt: null pointer");
-    BM_REQUIRE(M > 0 && Cn > 0 && T > 0 && G > 0 && nsplit > 0 && S >= 0, "gemm_nt: bad dims");
-    BM_REQUIRE(G == 1 || seg, "gemm_nt: grouped call needs seg[]");
     GemmNTArgs g;
-    g.a = a; g.a_sstride = a_sstride; g.a_rstride = a_rstride;
-    g.x = x; g.x_sstride = x_sstride; g.x_rstride = x_rstride;
-    g.order = order; g.seg = seg; g.part = part;
-    g.S = S; g.M = M; g.Cn = Cn; g.T = T; g.dil = dil; g.nsplit = nsplit; g.G = G;
-    hipStream_t s = (hipStream_t)stream;
-    const bool bigM = prefer_big(M);
-    if (KS == 1) {
-        const bool bigC = prefer_big(Cn);
-        if (bigM && bigC) return launch_gemm_nt<2, 2, 2, 2, 1>(g, s);
-        if (bigM) return launch_gemm_nt<2, 2, 2, 1, 1>(g, s);
-        if (bigC) return launch_gemm_nt<2, 2, 1, 2, 1>(g, s);
-        return launch_gemm_nt<2, 2, 1, 1, 1>(g, s);
-    }
-    if (KS == 3) {
-        if (bigM) return launch_gemm_nt<2, 2, 2, 1, 3>(g, s);
-        return launch_gemm_nt<2, 2, 1, 1, 3>(g, s);
-    }
-    if (KS == 5) return launch_gemm_nt<2, 2, 1, 1, 5>(g, s);
-    return bm_set_error(BM_ERR_UNSUPPORTED, "gemm_nt: kernel size %d not supported (1, 3, 5)", KS);
+    if (int e = gemm_nt_fill_args(g, GemmNTF32::name, a, a_sstride, a_rstride, x, x_sstride, x_rstride, order, seg, part,
+                                  S, G, M, Cn, T, dil, nsplit))
+        return e;
+    return gemm_nt_launch_tile<GemmNTF32>(g, KS, (hipStream_t)stream);
 }

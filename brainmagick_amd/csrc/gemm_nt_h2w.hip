@@ -36,7 +36,7 @@
 //   A [4 groups of 8 samples][64 MW + 2 rows], X [NS slots][4 groups][64 + 2 rows]   (row counts = 2 mod 8: the
 //   16 lanes of a ds_write_b64 group -- 2 rows x 8 pieces -- land on 16 different bank pairs).
 #include <cstdlib>
-#include "mfma_split.h"
+#include "gemm_nt_common.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -599,7 +599,6 @@ extern "C" int bm_gemm_nt_h2_covers(int M, int Cn, int KS, int S, int T, int G, 
 }
 
 // one workgroup per CU per round (256 CUs), >= 8 stages (of 32 samples) per workgroup
-extern "C" int bm_gemm_nt_h2_suggest_splits_grouped(int M, int Cn, int KS, int S, int T, int G);
 extern "C" int bm_gemm_nt_h2_suggest_splits(int M, int Cn, int KS, int S, int T) {
     return bm_gemm_nt_h2_suggest_splits_grouped(M, Cn, KS, S, T, 1);
 }
@@ -632,10 +631,6 @@ static int launch_gemm_nt_h2w(GemmNTArgsH g, hipStream_t stream, int ngroups = 1
     hipLaunchKernelGGL((gemm_nt_h2w_kernel<KS, MW, NS, RS, TS, FL>), dim3((unsigned)nblocks), dim3(256), lds, stream, g);
     return bm_check_launch("gemm_nt_h2w");
 }
-
-extern "C" int bm_gemm_nt_x3(const float* a, long a_sstride, long a_rstride, const float* x, long x_sstride,
-                             long x_rstride, const int* order, const int* seg, float* part, int S, int G, int M, int Cn,
-                             int T, int KS, int dil, int nsplit, void* stream);
 
 static int gemm_nt_h2_impl(const float* a, long a_sstride, long a_rstride, const float* a_amax, const float* a_row_amax,
                            const float* x, long x_sstride, long x_rstride, const float* x_amax, float* part, int S,

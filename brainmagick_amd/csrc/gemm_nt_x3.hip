@@ -7,35 +7,24 @@
 //
 // LDS: rows of 32 samples = 4 slots of 16 bytes, slot index XOR-swizzled with bits 2-3 of the row so that
 // both the row-per-lane ds_read_b128 of the MFMA operands and the 8-lane ds_write_b128 groups of the
-// staging pass are bank-conflict free (a +1 pad slot made the writes 2-way); three planes per operand, one pre-shifted copy of the X tile per tap (as in
-// gemm_nt_bf16.hip).  Software pipeline, split-K, grouping and XCD mapping as in gemm_nt.hip.
-#include "mfma_split.h"
+// staging pass are bank-conflict free (a +1 pad slot made the writes 2-way); three planes per operand, one pre-shifted
+// copy of the X tile per tap.  Software pipeline as in gemm_nt.hip; split-K, grouping, XCD mapping and the partial
+// tiles are gemm_nt_common.h's.
+#include "gemm_nt_common.h"
 
-#define BKT2 32
-#define SLOTS 4          // 4 data slots per row, XOR-swizzled: slot (row, q) lives at row*4 + (q ^ ((row >> 2) & 3))
-#define DSL 4            // data slots per row
+#define SLOTS 4          // 16-byte data slots per row, XOR-swizzled: slot (row, q) lives at row*4 + (q ^ ((row >> 2) & 3))
 #define SWZ(ROW_, Q_) ((ROW_) * SLOTS + ((Q_) ^ (((ROW_) >> 2) & 3)))
 
-struct GemmNTArgsX {
-    const float* a; long a_sstride; long a_rstride;
-    const float* x; long x_sstride; long x_rstride;
-    const int* order;
-    const int* seg;
-    float* part;
-    int S, M, Cn, T, dil, nsplit, G;
-    int tiles_m, tiles_c;
-};
-
 template <int WM, int WC, int MT, int NT, int KS>
-__global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gemm_nt_x3_kernel(GemmNTArgsX a) {
+__global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gemm_nt_x3_kernel(GemmNTArgs a) {
     constexpr int NW = WM * WC;
     constexpr int NTH = NW * 64;
     constexpr int BM = WM * MT * 32;
     constexpr int BC = WC * NT * 32;
-    constexpr int AIT = BM * DSL / NTH;               // 8-sample items per thread (A)
-    constexpr int XPT = BC * DSL / NTH;               // 8-sample items per thread and tap (X)
+    constexpr int AIT = BM * SLOTS / NTH;             // 8-sample items per thread (A)
+    constexpr int XPT = BC * SLOTS / NTH;             // 8-sample items per thread and tap (X)
     constexpr int XIT = KS * XPT;
-    static_assert((BM * DSL) % NTH == 0 && (BC * DSL) % NTH == 0, "tiles must split evenly over the threads");
+    static_assert((BM * SLOTS) % NTH == 0 && (BC * SLOTS) % NTH == 0, "tiles must split evenly over the threads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     u32x4* As = reinterpret_cast<u32x4*>(smem);       // [3 planes][BM][SLOTS]
     u32x4* Xs = As + 3 * BM * SLOTS;                  // [3 planes][KS][BC][SLOTS]
@@ -46,32 +35,15 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
     const int wm = wave / WC, wc = wave % WC;
     const int nl = lane & 31, h = lane >> 5;
 
-    int id = bm_xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = id % a.tiles_m; id /= a.tiles_m;
-    const int tc = id % a.tiles_c; id /= a.tiles_c;
-    const int split = id % a.nsplit;
-    const int g = id / a.nsplit;
-    const int m0 = tm * BM, c0 = tc * BC;
-
-    const int s_begin = a.seg ? a.seg[g] : 0;
-    const int s_end = a.seg ? a.seg[g + 1] : a.S;
-    const int cps = (a.T + BKT2 - 1) / BKT2;
-    const long nchunks = (long)(s_end - s_begin) * cps;
-    const long q_begin = nchunks * split / a.nsplit;
-    const long q_end = nchunks * (split + 1) / a.nsplit;
+    const GemmNTWork w = gemm_nt_work<BM, BC>(a);
+    const int m0 = w.m0, c0 = w.c0, s_begin = w.s_begin, cps = w.cps;
+    const long q_begin = w.q_begin, q_end = w.q_end;
     const int halo = (KS >> 1) * a.dil;
     const int a_bytes = (int)(((long)(a.M - 1) * a.a_rstride + a.T) * 4);
     const int x_bytes = (int)(((long)(a.Cn - 1) * a.x_rstride + a.T) * 4);
 
     f32x16 acc[MT][NT][KS];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-#pragma unroll
-            for (int j = 0; j < KS; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][k][j][r] = 0.f;
+    gemm_nt_zero(acc);
 
     typename FVec<8 * AIT>::type areg;
     typename FVec<8 * XIT>::type xreg;
@@ -114,12 +86,12 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
     }
 #define NT_LOAD()        /* stages chunk (ld_s, ld_c) and advances the cursor */                  \
     {                                                                                             \
-        const int t0 = ld_c * BKT2;                                                               \
+        const int t0 = ld_c * BKT;                                                                \
         int sidx = s_begin + ld_s;                                                                \
         if (a.order) sidx = a.order[sidx];                                                        \
         const __amdgpu_buffer_rsrc_t ra = bm_buffer_rsrc(a.a + (long)sidx * a.a_sstride, a_bytes);\
         const __amdgpu_buffer_rsrc_t rx = bm_buffer_rsrc(a.x + (long)sidx * a.x_sstride, x_bytes);\
-        if (t0 - halo < 0 || t0 + BKT2 + halo > a.T) {                                            \
+        if (t0 - halo < 0 || t0 + BKT + halo > a.T) {                                             \
             _Pragma("unroll") for (int i = 0; i < AIT; ++i)                                       \
                 LOAD8E(areg, 8 * i, ra, a_off[i] + t0, t0 + 8 * ((tid + i * NTH) & 3))            \
             _Pragma("unroll") for (int j = 0; j < KS; ++j) {                                      \
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
         const int sw = (nl >> 2) & 3;
         constexpr int APL = BM * SLOTS, XPL = KS * BC * SLOTS;      // plane strides
 #pragma unroll
-        for (int kk = 0; kk < BKT2 / 16; ++kk) {
+        for (int kk = 0; kk < BKT / 16; ++kk) {
             bf16x8 ah[MT], am[MT], al[MT];
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
@@ -220,78 +192,33 @@ __global__ __launch_bounds__(WM * WC * 64, (MT * NT * KS <= 3) ? 3 : 2) void gem
 #undef LOAD8
 #undef LOAD8E
 
-    const long N = (long)a.Cn * KS;
-    float* dst = a.part + (long)(g * a.nsplit + split) * a.M * N;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            const int c = c0 + wc * NT * 32 + k * 32 + nl;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < a.M && c < a.Cn) {
-#pragma unroll
-                    for (int j = 0; j < KS; ++j) dst[(long)m * N + (long)c * KS + j] = acc[i][k][j][r];
-                }
-            }
-        }
+    gemm_nt_store_partial<WM, WC, MT, NT, KS>(a, w, acc);
 }
 
-template <int WM, int WC, int MT, int NT, int KS>
-static int launch_gemm_nt_x3(GemmNTArgsX a, hipStream_t stream) {
-    constexpr int BM = WM * MT * 32, BC = WC * NT * 32;
-    const size_t lds = (size_t)3 * (BM + KS * BC) * SLOTS * 16;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_x3_kernel<WM, WC, MT, NT, KS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return bm_set_error((int)e, "gemm_nt_x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
+struct GemmNTX3 {
+    static constexpr const char* name = "gemm_nt_x3";
+    template <int WM, int WC, int MT, int NT, int KS>
+    static int launch(const GemmNTArgs& a, hipStream_t stream) {
+        constexpr int BM = WM * MT * 32, BC = WC * NT * 32;
+        return gemm_nt_launch(gemm_nt_x3_kernel<WM, WC, MT, NT, KS>, a, BM, BC, WM * WC * 64,
+                              (size_t)3 * (BM + KS * BC) * SLOTS * 16, name, stream);
     }
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_c = cdiv(a.Cn, BC);
-    const long nblocks = (long)a.tiles_m * a.tiles_c * a.nsplit * a.G;
-    if (nblocks <= 0) return BM_OK;
-    hipLaunchKernelGGL((gemm_nt_x3_kernel<WM, WC, MT, NT, KS>), dim3((unsigned)nblocks),
-                       dim3(WM * WC * 64), lds, stream, a);
-    return bm_check_launch("gemm_nt_x3");
-}
-
-extern "C" int bm_gemm_nt(const float* a, long a_sstride, long a_rstride, const float* x, long x_sstride,
-                          long x_rstride, const int* order, const int* seg, float* part, int S, int G, int M,
-                          int Cn, int T, int KS, int dil, int nsplit, void* stream);   // gemm_nt.hip
+};
 
 // Same contract as bm_gemm_nt (fp32 partial tiles out); fp32-accurate 3-plane bf16 emulation.
 extern "C" int bm_gemm_nt_x3(const float* a, long a_sstride, long a_rstride, const float* x,
                                long x_sstride, long x_rstride, const int* order, const int* seg,
                                float* part, int S, int G, int M, int Cn, int T, int KS, int dil,
                                int nsplit, void* stream) {
-    BM_REQUIRE(a && x && part, "gemm_nt_x3: null pointer");
-    BM_REQUIRE(M > 0 && Cn > 0 && T > 0 && G > 0 && nsplit > 0 && S >= 0, "gemm_nt_x3: bad dims");
-    BM_REQUIRE(G == 1 || seg, "gemm_nt_x3: grouped call needs seg[]");
+    GemmNTArgs g;
+    if (int e = gemm_nt_fill_args(g, GemmNTX3::name, a, a_sstride, a_rstride, x, x_sstride, x_rstride, order, seg, part,
+                                  S, G, M, Cn, T, dil, nsplit))
+        return e;
     // The staging addresses are 32-bit byte offsets into one segment (buffer descriptors).  An operand whose
     // segment spans 2 GB or more (e.g. 2 048 wav2vec candidates x 368 640 samples on 8 GPUs) goes through the
     // exact-fp32 kernel, which addresses with 64-bit pointers (same contract, at least as accurate).
     if (((long)(M - 1) * a_rstride + T) * 4 >= 0x7fffff00L || ((long)(Cn - 1) * x_rstride + T) * 4 >= 0x7fffff00L)
         return bm_gemm_nt(a, a_sstride, a_rstride, x, x_sstride, x_rstride, order, seg, part, S, G, M, Cn, T, KS,
                           dil, nsplit, stream);
-    GemmNTArgsX g;
-    g.a = a; g.a_sstride = a_sstride; g.a_rstride = a_rstride;
-    g.x = x; g.x_sstride = x_sstride; g.x_rstride = x_rstride;
-    g.order = order; g.seg = seg; g.part = part;
-    g.S = S; g.M = M; g.Cn = Cn; g.T = T; g.dil = dil; g.nsplit = nsplit; g.G = G;
-    hipStream_t s = (hipStream_t)stream;
-    const bool bigM = prefer_big(M);
-    if (KS == 1) {
-        const bool bigC = prefer_big(Cn);
-        if (bigM && bigC) return launch_gemm_nt_x3<2, 2, 2, 2, 1>(g, s);
-        if (bigM) return launch_gemm_nt_x3<2, 2, 2, 1, 1>(g, s);
-        if (bigC) return launch_gemm_nt_x3<2, 2, 1, 2, 1>(g, s);
-        return launch_gemm_nt_x3<2, 2, 1, 1, 1>(g, s);
-    }
-    if (KS == 3) {
-        if (bigM) return launch_gemm_nt_x3<2, 2, 2, 1, 3>(g, s);
-        return launch_gemm_nt_x3<2, 2, 1, 1, 3>(g, s);
-    }
-    if (KS == 5) return launch_gemm_nt_x3<2, 2, 1, 1, 5>(g, s);
-    return bm_set_error(BM_ERR_UNSUPPORTED, "gemm_nt_x3: kernel size %d not supported (1, 3, 5)", KS);
+    return gemm_nt_launch_tile<GemmNTX3>(g, KS, (hipStream_t)stream);
 }

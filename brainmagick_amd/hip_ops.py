@@ -578,6 +578,85 @@ def group_by_index(idx: torch.Tensor, G: int):
     return order, seg
 
 
+# The "NT" time contractions (csrc/gemm_nt*.hip).  Which kernel family serves a call, whether its operands are swapped
+# and how many ways its reduction is split is decided in ONE place, _nt_plan; _nt_launch issues what it decided.
+# Families: "f32" / "f32x3" (bm_gemm_nt / bm_gemm_nt_x3, any shape), and the wide f16x2 tiles "h2", "h2_rows",
+# "h2_grouped" (bm_gemm_nt_h2*) and "scores" (bm_clip_scores_h2), which cover only some shapes.
+_NT_SUFFIX = {"f32": "", "f32x3": "_x3"}        # family -> kernel family in the timer's labels (the wide tiles: "_h2w")
+
+
+def _nt_plan(M, Cn, KS, S, T, G, dil, grouped, a_strides, x_strides, nsplit=None, partials=False):
+    """(family, operands swapped, nsplit) of one contraction; ``partials``: the caller consumes the partial tiles
+    themselves (the ClipLoss scores, one group, KS = 1).  A caller's ``nsplit`` is kept."""
+    L = lib()
+    family, swapped = _compute_dtype, False
+    if family == "f16x2":
+        family = "f32x3"        # shapes without a wide f16x2 kernel: the (equally fp32-accurate) 3 x bf16 kernels
+        if partials:
+            if L.bm_gemm_nt_h2_covers(M, Cn, 1, S, T, 1, 1, 0):
+                # the score contraction proper (dense [M][T] x [Cn][T]): 256 x 256 tiles, transposed vector stores
+                dense = S == 1 and tuple(a_strides) == (0, T) and tuple(x_strides) == (0, T)
+                family = "scores" if dense and L.bm_clip_scores_h2_covers(M, Cn, T) else "h2"
+        # rows T apart; the segment stride only matters when there is more than one segment
+        elif a_strides[1] == T and x_strides[1] == T and \
+                (S == 1 or (a_strides[0] == M * T and x_strides[0] == Cn * T)):
+            # sum_t a[m][t] x[c][t] is symmetric in its operands: with the roles swapped the (M, Cn) rectangle may fit
+            # the wide tiles (208 x 270 per (layout, subject) pair: 256 x 128 tiles) where (270, 208) does not
+            covered = bool(L.bm_gemm_nt_h2_covers(M, Cn, KS, S, T, G, dil, int(grouped)))
+            swapped = not covered and KS == 1 and bool(L.bm_gemm_nt_h2_covers(Cn, M, KS, S, T, G, dil, int(grouped)))
+            if swapped:
+                M, Cn = Cn, M
+            if covered or swapped:
+                family = "h2_grouped" if grouped else "h2_rows"
+    if nsplit is None:
+        if family == "scores":
+            nsplit = L.bm_clip_scores_h2_suggest_splits(M, Cn, T)
+        elif partials:
+            nsplit = L.bm_gemm_nt_h2_suggest_splits(M, Cn, 1, S, T) if family == "h2" else \
+                L.bm_clip_suggest_splits(M, Cn, S, T)
+        elif family in _NT_SUFFIX:
+            nsplit = L.bm_gemm_nt_suggest_splits(M, Cn, KS, S, T, G)
+        else:
+            nsplit = L.bm_gemm_nt_h2_suggest_splits_grouped(M, Cn, KS, S, T, G)
+    return family, swapped, nsplit
+
+
+def _nt_launch(family, label, a, x, part, S, G, M, Cn, T, KS, dil, a_strides, x_strides, order, seg, nsplit):
+    """part[g, split][m][c*KS + j] (family "scores": [split][m][c]) by the entry point of ``family``, timed as ``label``."""
+    L = lib()
+    if family in _NT_SUFFIX:
+        fn = L.bm_gemm_nt if family == "f32" else L.bm_gemm_nt_x3
+
+        def launch():
+            check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1],
+                     _p(_opt(order, "order", torch.int32)), _p(_opt(seg, "seg", torch.int32)), _p(part), S,
+                     G, M, Cn, T, KS, dil, nsplit, _stream()), "bm_gemm_nt")
+    else:
+        a_amax, x_amax = amax(a), amax(x)
+        a_rows = row_amax_of(a) if family == "h2_rows" else None    # published by the producer of `a` (act_bn_bwd / glu_bwd)
+        if a_rows is not None and a_rows.numel() != M:
+            a_rows = None
+
+        def launch():
+            if family == "scores":
+                check(L.bm_clip_scores_h2(_p(a), _p(a_amax), _p(x), _p(x_amax), _p(part), M, Cn, T, nsplit, _stream()),
+                      "bm_clip_scores_h2")
+            elif family == "h2_grouped":
+                check(L.bm_gemm_nt_h2_grouped(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(x), x_strides[0],
+                                              x_strides[1], _p(x_amax), _p(_opt(order, "order", torch.int32)),
+                                              _p(_opt(seg, "seg", torch.int32)), _p(part), S, G, M, Cn, T, nsplit,
+                                              _stream()), "bm_gemm_nt_h2_grouped")
+            elif family == "h2_rows":
+                check(L.bm_gemm_nt_h2_rows(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(a_rows), _p(x),
+                                           x_strides[0], x_strides[1], _p(x_amax), _p(part), S, M, Cn, T, KS, dil,
+                                           nsplit, _stream()), "bm_gemm_nt_h2")
+            else:
+                check(L.bm_gemm_nt_h2(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(x), x_strides[0],
+                                      x_strides[1], _p(x_amax), _p(part), S, M, Cn, T, KS, dil, nsplit, _stream()),
+                      "bm_gemm_nt_h2")
+    _timed(label.format(_NT_SUFFIX.get(family, "_h2w")), 2.0 * S * T * M * Cn * KS, launch)
+
+
 def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, KS: int = 1,
             dil: int = 1, a_strides=None, x_strides=None, order=None, seg=None, G: int = 1,
             out: tp.Optional[torch.Tensor] = None, out_strides=None, nsplit: tp.Optional[int] = None):
@@ -595,62 +674,18 @@ def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, K
         out_strides = (M * Cn * KS, Cn * KS, KS, 1)
     if out is None:
         out = torch.empty(G, M, Cn, KS, device=a.device, dtype=torch.float32)
-    mode = _compute_dtype
     grouped = order is not None or seg is not None
-    if mode == "f16x2":
-        # rows T apart; the segment stride only matters when there is more than one segment
-        contiguous = a_strides[1] == T and x_strides[1] == T and \
-            (S == 1 or (a_strides[0] == M * T and x_strides[0] == Cn * T))
-        covered = contiguous and lib().bm_gemm_nt_h2_covers(M, Cn, KS, S, T, G, dil, int(grouped))
-        if contiguous and not covered and KS == 1 and lib().bm_gemm_nt_h2_covers(Cn, M, KS, S, T, G, dil, int(grouped)):
-            # sum_t a[m][t] x[c][t] is symmetric in its operands: with the roles swapped the (M, Cn) rectangle may fit
-            # the wide tiles (208 x 270 per (layout, subject) pair: 256 x 128 tiles) where (270, 208) does not --
-            # the result lands through the swapped output strides
-            a, x, M, Cn, a_strides, x_strides = x, a, Cn, M, x_strides, a_strides
-            out_strides = (out_strides[0], out_strides[2], out_strides[1], out_strides[3])
-            covered = True
-        if not covered:
-            mode = "f32x3"      # shapes without a wide f16x2 kernel: the (equally fp32-accurate) 3 x bf16 kernels
-        elif nsplit is None:
-            nsplit = lib().bm_gemm_nt_h2_suggest_splits_grouped(M, Cn, KS, S, T, G)
-    if nsplit is None:
-        nsplit = lib().bm_gemm_nt_suggest_splits(M, Cn, KS, S, T, G)
-        if G > 1:
-            # grouped (per-subject / per-layout) weight gradients run in the 160 x 128-tile kernels, two workgroups
-            # per CU: split each group's (segment, 32-sample chunk) list until ~512 workgroups exist, keeping at
-            # least 8 chunks per split
-            tiles = -(-M // 160) * -(-Cn // 128) * G
-            chunks = max(1, S // G) * -(-T // 32)
-            nsplit = max(1, min(8, 512 // tiles, chunks // 8))
+    family, swapped, nsplit = _nt_plan(M, Cn, KS, S, T, G, dil, grouped, a_strides, x_strides, nsplit)
+    if swapped:         # the result lands through the swapped output strides
+        a, x, M, Cn, a_strides, x_strides = x, a, Cn, M, x_strides, a_strides
+        out_strides = (out_strides[0], out_strides[2], out_strides[1], out_strides[3])
     canonical = tuple(out_strides) == (M * Cn * KS, Cn * KS, KS, 1)
     if nsplit == 1 and canonical:
         part = out
     else:
         part = torch.empty(G * nsplit * M * Cn * KS, device=a.device, dtype=torch.float32)
-    if mode == "f16x2":
-        a_amax, x_amax = amax(a), amax(x)
-        a_rows = row_amax_of(a)          # published by the producer of `a` (act_bn_bwd / glu_bwd)
-        if a_rows is not None and a_rows.numel() != M:
-            a_rows = None
-
-        def launch():
-            if grouped:
-                check(lib().bm_gemm_nt_h2_grouped(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(x), x_strides[0],
-                                                  x_strides[1], _p(x_amax), _p(_opt(order, "order", torch.int32)),
-                                                  _p(_opt(seg, "seg", torch.int32)), _p(part), S, G, M, Cn, T, nsplit,
-                                                  _stream()), "bm_gemm_nt_h2_grouped")
-                return
-            check(lib().bm_gemm_nt_h2_rows(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(a_rows), _p(x),
-                                           x_strides[0], x_strides[1], _p(x_amax), _p(part), S, M, Cn, T, KS, dil,
-                                           nsplit, _stream()), "bm_gemm_nt_h2")
-    else:
-        fn = {"f32": lib().bm_gemm_nt, "f32x3": lib().bm_gemm_nt_x3}[mode]
-
-        def launch():
-            check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1],
-                     _p(_opt(order, "order", torch.int32)), _p(_opt(seg, "seg", torch.int32)), _p(part), S,
-                     G, M, Cn, T, KS, dil, nsplit, _stream()), "bm_gemm_nt")
-    _timed(f"gemm_nt{_MODE_SUFFIX[mode]}_kernel<KS={KS}>", 2.0 * S * T * M * Cn * KS, launch)
+    _nt_launch(family, f"gemm_nt{{}}_kernel<KS={KS}>", a, x, part, S, G, M, Cn, T, KS, dil, a_strides, x_strides,
+               order, seg, nsplit)
     if part is not out:
         check(lib().bm_reduce_splits(_p(part), _p(out), G, nsplit, M, Cn, KS, *out_strides,
                                      _stream()), "bm_reduce_splits")
@@ -699,39 +734,9 @@ def gemm_nt_partials(a, x, S, M, Cn, T, a_strides, x_strides, nsplit=None):
     """Split-K partial tiles [nsplit][M][Cn] (KS=1, one group), consumed by clip_ce."""
     _req(a, "gemm_nt.a")
     _req(x, "gemm_nt.x")
-    mode = _compute_dtype
-    if mode == "f16x2" and not lib().bm_gemm_nt_h2_covers(M, Cn, 1, S, T, 1, 1, 0):
-        mode = "f32x3"
-    # the score contraction proper (dense [M][T] x [Cn][T]): 256 x 256 tiles, transposed vector stores
-    scores_kernel = mode == "f16x2" and S == 1 and tuple(a_strides) == (0, T) and tuple(x_strides) == (0, T) and \
-        bool(lib().bm_clip_scores_h2_covers(M, Cn, T))
-    if nsplit is None:
-        if scores_kernel:
-            nsplit = lib().bm_clip_scores_h2_suggest_splits(M, Cn, T)
-        else:
-            nsplit = lib().bm_gemm_nt_h2_suggest_splits(M, Cn, 1, S, T) if mode == "f16x2" else \
-                lib().bm_clip_suggest_splits(M, Cn, S, T)
+    family, _, nsplit = _nt_plan(M, Cn, 1, S, T, 1, 1, False, a_strides, x_strides, nsplit, partials=True)
     part = torch.empty(nsplit, M, Cn, device=a.device, dtype=torch.float32)
-    if scores_kernel:
-        a_amax, x_amax = amax(a), amax(x)
-
-        def launch():
-            check(lib().bm_clip_scores_h2(_p(a), _p(a_amax), _p(x), _p(x_amax), _p(part), M, Cn, T, nsplit, _stream()),
-                  "bm_clip_scores_h2")
-    elif mode == "f16x2":
-        a_amax, x_amax = amax(a), amax(x)
-
-        def launch():
-            check(lib().bm_gemm_nt_h2(_p(a), a_strides[0], a_strides[1], _p(a_amax), _p(x), x_strides[0],
-                                      x_strides[1], _p(x_amax), _p(part), S, M, Cn, T, 1, 1, nsplit, _stream()),
-                  "bm_gemm_nt_h2")
-    else:
-        fn = lib().bm_gemm_nt_x3 if mode == "f32x3" else lib().bm_gemm_nt
-
-        def launch():
-            check(fn(_p(a), a_strides[0], a_strides[1], _p(x), x_strides[0], x_strides[1], None, None, _p(part),
-                     S, 1, M, Cn, T, 1, 1, nsplit, _stream()), "bm_gemm_nt")
-    _timed("clip_scores:gemm_nt" + _MODE_SUFFIX[mode], 2.0 * S * T * M * Cn, launch)
+    _nt_launch(family, "clip_scores:gemm_nt{}", a, x, part, S, 1, M, Cn, T, 1, 1, a_strides, x_strides, None, None, nsplit)
     return part
 
 

@@ -206,7 +206,11 @@ int bm_clip_scores_h2(const float* est, const float* est_amax, const float* cand
 /* ---- time-contraction GEMM, fp32 MFMA, split-K (gemm_nt.hip) ----
  * part[g,split][m][c*KS+j] = sum_{s in group g} sum_t A[s][m][t] * X[s][c][t + (j-KS/2)*dil].
  * Replaces aten::convolution_backward (weight part), the weight-grad einsums of SubjectLayers /
- * ChannelMerger, torch.einsum("bct,oct,o->bo") (losses.py:94) and einsum("bcd,bod->boc") (common.py:355). */
+ * ChannelMerger, torch.einsum("bct,oct,o->bo") (losses.py:94) and einsum("bcd,bod->boc") (common.py:355).
+ * bm_gemm_nt_suggest_splits: the split count of bm_gemm_nt / bm_gemm_nt_x3 for one group (G = 1: ~4 workgroups per
+ * CU, >= 8 chunks of 32 samples each) and for G > 1 groups of ~S / G segments (splits per group, at most 8; its
+ * constants are historical and fixed, they determine the summation order of the grouped gradients).
+ * bm_clip_suggest_splits: the same for the ClipLoss score contraction, whose partial tiles are read back. */
 int bm_gemm_nt_suggest_splits(int M, int Cn, int KS, int S, int T, int G);
 int bm_clip_suggest_splits(int M, int Cn, int S, int T);
 int bm_gemm_nt(const float* a, long a_sstride, long a_rstride, const float* x, long x_sstride,

@@ -48,6 +48,15 @@ def test_conv_backward_x3(x3_mode, H, Cin, M, KS, dil, T, B):
     TK.test_conv_backward_kernels(H, Cin, M, KS, dil, T, B)
 
 
+@pytest.mark.parametrize("S,M,Cn,T,KS,dil", TK.NT_CASES)
+def test_gemm_nt_tiles_and_windows_x3(x3_mode, H, S, M, Cn, T, KS, dil):
+    TK.test_gemm_nt_tiles_and_windows(H, S, M, Cn, T, KS, dil)
+
+
+def test_subject_layers_grouped_gradient_with_splits_x3(x3_mode, H):
+    TK.test_subject_layers_grouped_gradient_with_splits(H)
+
+
 def test_x3_error_is_fp32_class(H):
     """Error vs fp64 of the x3 path next to the exact-fp32 MFMA path on the same inputs, and proof that
     the three bf16 planes are really used (a single-plane bf16 result would be ~2e-3 off)."""

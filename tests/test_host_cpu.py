@@ -723,9 +723,58 @@ def test_score_kernel_shape_rules():
     assert L.bm_conv_h2_stats_tiles(256, 360) == 256 * 2 * 2
 
 
+def test_gemm_nt_split_rule():
+    """`bm_gemm_nt_suggest_splits` (no GPU needed).  Grouped calls (G > 1): every group's (segment, chunk) list is split
+    until ~512 workgroups exist, counted in 160 x 128 tiles, at most 8 ways and with at least 8 chunks per split --
+        tiles = cdiv(M, 160) cdiv(Cn, 128) G,   chunks = max(1, S // G) cdiv(T, 32),
+        nsplit = max(1, min(8, 512 // tiles, chunks // 8))
+    -- the rule that `hip_ops.gemm_nt` used to apply on top of the library's; its constants fix the summation order of
+    the grouped gradients.  One group: the library's rule as it was, transcribed below."""
+    from brainmagick_amd import _lib
+    L = _lib.lib()
+
+    def cdiv(a, b):
+        return -(-a // b)
+
+    def grouped(M, Cn, KS, S, T, G):
+        tiles = cdiv(M, 160) * cdiv(Cn, 128) * G
+        chunks = max(1, S // G) * cdiv(T, 32)
+        return max(1, min(8, 512 // tiles, chunks // 8))
+
+    def prefer_big(n):
+        return cdiv(n, 128) * 128 <= cdiv(n, 64) * 64
+
+    def one_group(M, Cn, KS, S, T):
+        if KS == 1:
+            tiles = cdiv(M, 128 if prefer_big(M) else 64) * cdiv(Cn, 128 if prefer_big(Cn) else 64)
+        else:
+            tiles = cdiv(M, 128 if prefer_big(M) else 64) * cdiv(Cn, 64)
+        chunks = S * cdiv(T, 32)
+        want = (1024 + tiles - 1) // tiles
+        if want > chunks // 8:
+            want = chunks // 8
+        if want < 1:
+            want = 1
+        if want > 256:
+            want = 256
+        return want
+
+    # worked out by hand from the formula: the SubjectLayers test shape, the per-(layout, subject) and the per-layout
+    # gradients of the production front end
+    assert L.bm_gemm_nt_suggest_splits(45, 37, 1, 9, 120, 4) == 1
+    assert L.bm_gemm_nt_suggest_splits(320, 270, 1, 256, 360, 27) == 3
+    assert L.bm_gemm_nt_suggest_splits(270, 208, 1, 256, 360, 4) == 8
+    shapes = [(M, Cn, KS, S, T) for M in (1, 40, 65, 128, 320, 1024) for Cn in (1, 20, 100, 270, 960)
+              for KS in (1, 3, 5) for S in (1, 9, 256) for T in (7, 50, 360, 92160)]
+    for M, Cn, KS, S, T in shapes:
+        assert L.bm_gemm_nt_suggest_splits(M, Cn, KS, S, T, 1) == one_group(M, Cn, KS, S, T), (M, Cn, KS, S, T)
+        for G in (2, 4, 27, 300):
+            assert L.bm_gemm_nt_suggest_splits(M, Cn, KS, S, T, G) == grouped(M, Cn, KS, S, T, G), (M, Cn, KS, S, T, G)
+
+
 def test_header_prototypes_match_the_definitions():
-    """`include/bm_hip.h` is what `_lib.py` parses into ctypes prototypes, but the kernels' translation units do not
-    include it -- a drifted parameter list would silently pass mis-typed arguments.  Every `extern "C"` definition of
+    """`include/bm_hip.h` is what `_lib.py` parses into ctypes prototypes, but most of the kernels' translation units
+    do not include it (those of the gemm_nt family do) -- a drifted parameter list would silently pass mis-typed arguments.  Every `extern "C"` definition of
     csrc/*.hip is re-declared next to the header in one translation unit; C linkage forbids overloads, so g++ rejects
     any definition whose parameter types differ from the header's."""
     import tempfile

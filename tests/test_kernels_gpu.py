@@ -141,6 +141,62 @@ def test_subject_layers_kernels(H):
     assert torch.count_nonzero(dW[1]) == 0
 
 
+def test_subject_layers_grouped_gradient_with_splits(H):
+    """The grouped weight gradient of `test_subject_layers_kernels` (same inputs: B = 9, four groups, one of them empty)
+    with every group's (segment, chunk) list cut into three splits."""
+    g = _gen(3)
+    B, C, D, T, S = 9, 37, 45, 120, 4
+    x = torch.randn(B, C, T, generator=g, dtype=torch.float64)
+    W = torch.randn(S, C, D, generator=g, dtype=torch.float64, requires_grad=True)
+    subj = torch.tensor([2, 0, 2, 3, 3, 3, 0, 2, 2])        # subject 1 is absent from the batch
+    dy = torch.randn(B, D, T, generator=g, dtype=torch.float64)
+    O.subject_layers(x, W, subj).backward(dy)
+    order, seg = H.group_by_index(subj.cuda(), S)
+    dW = torch.full((S, C, D), float("nan"), device="cuda")
+    H.gemm_nt(dy.float().cuda(), x.float().cuda(), B, D, C, T, 1, 1, order=order, seg=seg, G=S, out=dW,
+              out_strides=(C * D, 1, D, 0), nsplit=3)
+    assert rel_l2(dW, W.grad) < GRAD_TOL
+    assert torch.count_nonzero(dW[1]) == 0
+
+
+NT_CASES = [
+    # S, M, Cn, T, KS, dil
+    (3, 40, 128, 50, 1, 1),     # tile <2,2,1,2,1> (64 rows, 128 columns); scalar staging, partial last chunk
+    (2, 128, 20, 64, 3, 1),     # tile <2,2,2,1,3>; vector staging, whole chunks only
+    (2, 24, 20, 100, 3, 20),    # halo 20: the 96-sample window of the fp32 kernel, edge-chunk loads of the x3 kernel
+    (2, 24, 20, 99, 3, 20),     # the same on the scalar path
+    (2, 24, 20, 100, 5, 5),     # 5 taps, halo 10
+    (2, 24, 20, 100, 3, 40),    # halo 40: refused by the fp32 kernel, computed by the x3 kernel
+]
+
+
+@pytest.mark.parametrize("S,M,Cn,T,KS,dil", NT_CASES)
+def test_gemm_nt_tiles_and_windows(H, S, M, Cn, T, KS, dil):
+    """`H.gemm_nt` directly against out[m][c][j] = sum_{s,t} a[s][m][t] x[s][c][t + (j - KS/2) dil] in fp64 (x zero
+    outside [0, T)), at the tiles, staged windows and staging paths that the conv cases do not reach, with one and
+    with three splits, each computed twice (bit-identical).  These small shapes have no wide f16x2 kernel: the default
+    mode runs the 3 x bf16 kernels here, tests/test_exact_f32_gpu.py the exact-fp32 ones too."""
+    from brainmagick_amd._lib import BmHipError
+    g = _gen(S * 1000 + M + Cn + T + KS + dil)
+    a = torch.randn(S, M, T, generator=g)
+    x = torch.randn(S, Cn, T, generator=g)
+    halo = KS // 2 * dil
+    xpad = F.pad(x.double(), (halo, halo))
+    ref = torch.stack([torch.einsum("smt,sct->mc", a.double(), xpad[..., j * dil:j * dil + T]) for j in range(KS)], -1)
+    ag, xg = a.cuda(), x.cuda()
+    for nsplit in (1, 3):
+        if H.get_compute_dtype() == "f32" and halo > 32:
+            with pytest.raises(BmHipError, match="32-sample halo"):
+                H.gemm_nt(ag, xg, S, M, Cn, T, KS, dil, nsplit=nsplit)
+            continue
+        out = H.gemm_nt(ag, xg, S, M, Cn, T, KS, dil, nsplit=nsplit)
+        assert out.shape == (1, M, Cn, KS)
+        err = rel_l2(out[0], ref)
+        print(f"gemm_nt {H.get_compute_dtype()} {(S, M, Cn, T, KS, dil)} nsplit={nsplit}: rel-L2 {err:.3e}")
+        assert err < GRAD_TOL
+        assert torch.equal(out, H.gemm_nt(ag, xg, S, M, Cn, T, KS, dil, nsplit=nsplit))
+
+
 @pytest.mark.parametrize("train", [True, False])
 @pytest.mark.parametrize("B,C,T", [(256, 320, 360),      # the production shape: 10 splits of <= 26 segments per channel
                                    (173, 320, 360),      # ragged batch: splits of 17 / 18 segments
