@@ -136,7 +136,8 @@ class Conv1dFn(torch.autograd.Function):
                 pad=None):
         x, weight = _c(x), _c(weight)
         geom = (dil, transposed_weight, stride, pad)
-        need_pre = act != H.ACT_NONE and (x.requires_grad or weight.requires_grad)
+        # (the bias alone may be trainable: its gradient goes through the activation's backward, which reads `pre`)
+        need_pre = act != H.ACT_NONE and any(ctx.needs_input_grad[:3])
         if need_pre and pad is None:
             # training: the pre-activation is saved anyway; the activation as a streaming pass over it is cheaper
             # than the conv kernel's general epilogue (erf per accumulator element with the matrix cores idle)
@@ -180,7 +181,7 @@ class ConvBNActFn(torch.autograd.Function):
         x, weight = _c(x), _c(weight)
         geom = (dil, transposed, stride, pad)
         res = x if residual else None
-        needs_grad = x.requires_grad or weight.requires_grad
+        needs_grad = any(ctx.needs_input_grad[:5])      # x, weight, bias, gamma, beta: all go through `pre`
         if training:
             pre, _, stats = _layer_forward(x, weight, geom, bias=bias, want_pre=True, want_out=False, want_stats=True)
             mean, invstd, scale, shift = H.bn_finalize(stats, pre.shape[0] * pre.shape[2], gamma, beta, running_mean,

@@ -128,11 +128,14 @@ def conv_mpad(M: int) -> int:
 
 
 # A value that a kernel derived from a tensor's contents (its maximum, per-channel maxima, inverse row norms) is
-# remembered ON the tensor as (version, data_ptr, value[, checked]); it holds for exactly those contents.
+# remembered ON the tensor as (version, data_ptr, value[, checked]); it holds for exactly those contents.  A leaf that
+# requires grad is a parameter, which the library's own writers change through raw pointers (FlatAdam.step, the
+# data-parallel gathers: ``weights_changed()``): its notes hold for the weights epoch they were taken in (``_bm_epoch``).
 def _note(t: torch.Tensor, attr: str, value, *checked):
     try:
         setattr(t, attr, (t._version, t.data_ptr(), value) + checked)
-    except Exception:       # tensors that refuse attributes: just do not cache
+        t._bm_epoch = _weights_epoch
+    except Exception:       # tensors that refuse attributes or have no version counter (inference mode): do not cache
         pass
 
 
@@ -140,7 +143,8 @@ def _noted(t: torch.Tensor, attr: str, need_checked: bool = False):
     """The value noted on ``t`` if it still describes it, else None.  ``need_checked``: only a note taken together
     with the non-finite check will do."""
     note = getattr(t, attr, None)
-    if note is not None and note[0] == t._version and note[1] == t.data_ptr() and (not need_checked or note[3]):
+    if note is not None and note[0] == t._version and note[1] == t.data_ptr() and (not need_checked or note[3]) and \
+            (not (t.requires_grad and t.is_leaf) or getattr(t, "_bm_epoch", None) == _weights_epoch):
         return note[2]
     return None
 
@@ -674,6 +678,8 @@ def gemm_nt(a: torch.Tensor, x: torch.Tensor, S: int, M: int, Cn: int, T: int, K
         out_strides = (M * Cn * KS, Cn * KS, KS, 1)
     if out is None:
         out = torch.empty(G, M, Cn, KS, device=a.device, dtype=torch.float32)
+    else:
+        _touched(out)
     grouped = order is not None or seg is not None
     family, swapped, nsplit = _nt_plan(M, Cn, KS, S, T, G, dil, grouped, a_strides, x_strides, nsplit)
     if swapped:         # the result lands through the swapped output strides
@@ -1134,6 +1140,9 @@ def clip_ce_cols(scores, inv_norm, dscaled, loss, target_offset: int = 0, w_row:
     _req(scores, "clip_ce_cols.scores")
     B, Bc = scores.shape
     loss_col = torch.empty(B, device=scores.device, dtype=torch.float32)
+    for t in (dscaled, loss):
+        if t is not None:
+            _touched(t)
     check(lib().bm_clip_ce_cols(_p(scores), _p(_req(inv_norm, "inv_norm")), _p(_opt(dscaled, "dscaled")),
                                 _p(loss_col), _p(_opt(loss, "loss")), B, Bc, target_offset, w_row, w_col, _stream()),
           "bm_clip_ce_cols")
@@ -1303,6 +1312,8 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step: int, lr: float, beta1: flo
         _req(t, f"adam_step.{n}")
     check(lib().bm_adam_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), step,
                              lr, beta1, beta2, eps, grad_scale, _stream()), "bm_adam_step")
+    for t in (param, exp_avg, exp_avg_sq):
+        _touched(t)
     weights_changed()
 
 

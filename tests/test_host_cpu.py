@@ -950,3 +950,57 @@ def test_comm_timer_is_inert_without_a_gpu_and_names_the_phases(monkeypatch):
     finally:
         distrib.set_comm_timer(None)
     assert distrib.reported_world() == 1
+
+
+# hip_ops wrappers whose ``out`` / ``inplace`` parameter reaches a library call WITHOUT being a destination, or whose
+# destination is handled elsewhere: one reason each.
+_TOUCHED_EXEMPT = {
+    "regress_loss_fwd": "``out`` is the target tensor of the loss: the kernel only reads it",
+    "regress_loss_bwd": "``out`` is the target tensor again; the gradients are fresh tensors",
+    "regress_metric_update": "``out`` is the target tensor; the accumulator is fp64 and never a contraction operand",
+    "feature_decoding_fwd": "``out`` is the target tensor of the loss: only read",
+    "feature_decoding_bwd": "``out`` is the target tensor of the loss: only read",
+}
+
+
+def test_every_wrapper_that_writes_through_out_or_inplace_calls_touched():
+    """A kernel that stores into a caller's tensor through its raw pointer is invisible to torch's version counter: the
+    wrapper has to drop what was noted on the tensor (hip_ops._touched).  Walks hip_ops.py: every function with a
+    parameter named ``out`` or ``inplace`` whose body hands that parameter (for ``inplace``: the tensor it redirects the
+    output to) to a ``lib().bm_*`` call must call ``_touched``."""
+    import ast
+    tree = ast.parse((ROOT / "brainmagick_amd" / "hip_ops.py").read_text())
+
+    def names_in(node):
+        return {n.id for n in ast.walk(node) if isinstance(n, ast.Name)}
+
+    def is_lib_call(call):
+        f = call.func
+        return isinstance(f, ast.Attribute) and f.attr.startswith("bm_") and \
+            any(isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "lib" or
+                isinstance(n, ast.Name) and n.id == "L" for n in ast.walk(f.value))
+
+    checked, missing = [], []
+    for fn in [n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef)]:
+        params = {a.arg for a in fn.args.args + fn.args.kwonlyargs} & {"out", "inplace"}
+        if not params:
+            continue
+        # names that may alias the destination: the parameter itself and whatever is assigned from an expression using it
+        alias = set(params)
+        for node in ast.walk(fn):
+            if isinstance(node, ast.Assign) and names_in(node.value) & alias:
+                alias |= {t.id for t in node.targets if isinstance(t, ast.Name)}
+        reaches = any(isinstance(c, ast.Call) and is_lib_call(c) and names_in(ast.Module(body=[ast.Expr(a) for a in c.args],
+                                                                                       type_ignores=[])) & alias
+                      for c in ast.walk(fn))
+        if not reaches:
+            continue
+        checked.append(fn.name)
+        touches = any(isinstance(c, ast.Call) and isinstance(c.func, ast.Name) and c.func.id == "_touched" and
+                      (names_in(c) & alias or "inplace" in params) for c in ast.walk(fn))
+        if not touches and fn.name not in _TOUCHED_EXEMPT:
+            missing.append(fn.name)
+    assert not missing, f"write into a caller's tensor without _touched: {missing}"
+    for name in ("conv_nn", "conv_strided_wgrad", "gemm_nt", "center_scale", "center_scale_inverse"):
+        assert name in checked, (name, checked)           # the walk really sees the known writers
+    assert set(_TOUCHED_EXEMPT) <= set(checked), sorted(set(_TOUCHED_EXEMPT) - set(checked))

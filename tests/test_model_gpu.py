@@ -1528,6 +1528,50 @@ def test_flat_bucket_views_are_handed_out_only_inside_writing_grads():
     assert torch.equal(opt.flat_grad, direct)
 
 
+@pytest.mark.parametrize("how", ["two_micro_batches", "one_graph_uses_every_weight_twice", "second_backward_retained"])
+def test_flat_bucket_accumulates_like_fresh_gradients(how):
+    """One ``zero_grad(set_to_none=True)``, then under ONE ``writing_grads()``: two micro-batches (the bucket view is
+    handed out once, the second backward accumulates into it through autograd), one graph in which every weight takes
+    part twice, and a second backward over a retained graph.  ``flat_grad`` must equal, bit for bit, the fp32 sum of the
+    two gradients taken with fresh tensors (``torch.autograd.grad`` outside the context) -- exactly twice the first
+    gradient in the retained case."""
+    from brainmagick_amd.solver import Solver
+    model, _ = _small_model(merger_dropout=0.0)
+    solver = Solver(model)
+    opt = solver.optimizer
+    batches = [synthetic.make_batch(4, 20, 40, 10, 3, seed=8 + k) for k in range(2)]
+    if how == "second_backward_retained":
+        batches[1] = batches[0]
+
+    def loss_of(sb):
+        estimate, output, mask, _ = solver._process_batch(sb, training=True)
+        return solver.loss(estimate, output, mask)
+
+    opt.zero_grad(set_to_none=True)
+    fresh = [torch.autograd.grad(loss_of(sb), opt.params, allow_unused=True) for sb in batches]
+    want = torch.zeros_like(opt.flat_grad)
+    for p, off, g1, g2 in zip(opt.params, opt.offsets, *fresh):
+        assert (g1 is None) == (g2 is None)
+        if g1 is not None:
+            want[off:off + p.numel()] = (g1 + g2).reshape(-1)
+    lo, hi = opt.flat_grad.data_ptr(), opt.flat_grad.data_ptr() + 4 * opt.padded
+    opt.zero_grad(set_to_none=True)
+    with opt.writing_grads():
+        if how == "two_micro_batches":
+            loss_of(batches[0]).backward()
+            inside = sum(1 for p in opt.params if p.grad is not None and lo <= p.grad.data_ptr() < hi)
+            assert inside > 0, "no weight gradient was written straight into the bucket"
+            loss_of(batches[1]).backward()
+        elif how == "one_graph_uses_every_weight_twice":
+            (loss_of(batches[0]) + loss_of(batches[1])).backward()
+        else:
+            loss = loss_of(batches[0])
+            loss.backward(retain_graph=True)
+            loss.backward()
+    opt.collect_grads()
+    assert torch.equal(opt.flat_grad, want), (how, (opt.flat_grad - want).abs().max().item())
+
+
 def test_negative_pool_completes_the_candidates_like_the_reference():
     """bm/solver.py:358-371 (`optim.negatives`): a batch with fewer candidates than `n_negatives` is completed with
     a random draw (torch.randperm) from the pool of earlier candidate sets, and the pool takes the completed set in
