@@ -1024,6 +1024,37 @@ def regress_metric_update(est: torch.Tensor, out: torch.Tensor, mask: tp.Optiona
     return acc
 
 
+# The encode task's model input (csrc/encode.hip).
+_encode_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
+
+
+def _encode_ws(device) -> torch.Tensor:
+    """Ticket counter + partial maxima of ``bm_meg_init``: one ZEROED buffer per (device, stream); every launch leaves
+    its counter at zero again."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _encode_workspaces.get(key)
+    if ws is None:
+        ws = _encode_workspaces[key] = torch.zeros(lib().bm_meg_init_workspace_bytes(), device=device,
+                                                   dtype=torch.uint8)
+    return ws
+
+
+def meg_init(meg: torch.Tensor, limit: int) -> torch.Tensor:
+    """x = meg for the samples t < limit, 0 for the others (bm/solver.py:288-292, ``mask * meg``): contiguous fp32
+    [B, C, T] in, a new tensor out -- one launch that reads only the head and, in f16x2 mode, publishes max |x| (the
+    first layer needs no pass over a tensor that is mostly zeros).  The tail is +0.0 whatever ``meg`` holds there."""
+    _req(meg, "meg_init.meg")
+    if meg.dim() != 3:
+        raise BmHipError(f"meg_init: meg {tuple(meg.shape)} must be [B, C, T]")
+    B, C, T = meg.shape
+    x = torch.empty_like(meg)
+    slot = _amax_slot(x)
+    ws = _encode_ws(meg.device) if slot is not None else None
+    check(lib().bm_meg_init(_p(meg), _p(x), B, C, T, max(0, min(int(limit), T)), _p(slot), _p(ws), ws.numel() if ws is not None else 0,
+                            _stream()), "bm_meg_init")
+    return x
+
+
 # FeatureDecodingLoss / ClassificationAcc (csrc/regress.hip).  ``table``: one row per feature, (kind, est_start, width,
 # out_start, weight_off) with kind 0 = continuous, 1 = categorical (width = number of classes) and weight_off the
 # feature's offset into ``weights`` or -1.

@@ -80,11 +80,30 @@ class _ColumnSums(TestMetric):
         return self._acc
 
 
+def _common_window(tensors: tp.Sequence[torch.Tensor]):
+    """(base tensors, a) when every tensor is the same time window ``x[..., a:]`` (a > 0) of a contiguous 3-d tensor
+    ``x`` -- what ``Solver._process_batch`` returns for the encode task -- else None."""
+    bases, start = [], None
+    for t in tensors:
+        base = t._base
+        if base is None or t.dim() != 3 or base.dim() != 3 or not base.is_contiguous() or \
+                base.shape[:2] != t.shape[:2] or t.stride() != base.stride():
+            return None
+        a = t.storage_offset() - base.storage_offset()
+        if a <= 0 or a + t.shape[2] != base.shape[2] or (start is not None and a != start):
+            return None
+        start = a
+        bases.append(base)
+    return bases, start
+
+
 def update_all(metrics: tp.Sequence[TestMetric], left: torch.Tensor, right: torch.Tensor,
                mask: tp.Optional[torch.Tensor], t0: int = 0) -> None:
     """``metric.update(left, right, mask)`` for every metric, with ONE kernel pass per distinct pair of slices: metrics
     with the same slices that are always updated together share their accumulator (an L2Reg and an OnlineCorrelation of
-    one feature).  A ``ClassificationAcc`` in the list takes its own pass."""
+    one feature).  A ``ClassificationAcc`` in the list takes its own pass.  Operands that are all the same window
+    ``x[..., a:]`` of contiguous tensors are read in place: the kernels walk the base tensors from ``t0 + a``; any other
+    non-contiguous layout is copied once by the kernel wrappers."""
     for t, what in ((left, "left"), (right, "right")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"brainmagick_amd metrics run on the MI355X HIP path only (no CPU fallback): {what} is "
@@ -93,6 +112,11 @@ def update_all(metrics: tp.Sequence[TestMetric], left: torch.Tensor, right: torc
             raise TypeError(f"{what}: expected float32 (the kernel accumulates in float64), got {t.dtype}")
     if mask is not None and mask.dtype != torch.bool:
         raise TypeError(f"mask must be a bool tensor, got {mask.dtype}")
+    window = _common_window([left, right] + ([mask] if mask is not None else []))
+    if window is not None:
+        (left, right, *rest), start = window
+        mask = rest[0] if rest else None
+        t0 += start
     groups: tp.Dict[tp.Any, tp.List[_ColumnSums]] = {}
     for m in metrics:
         if isinstance(m, ClassificationAcc):
@@ -249,6 +273,19 @@ def regression_metric_constructors(feature_name: str, feature_slice: slice = sli
     reference's argument order (the L2 metric takes the feature slice first)."""
     return [L2Reg.get_constructor(feature_slice, model_out_slice, name=f"l2_{feature_name}"),
             OnlineCorrelation.get_constructor(model_out_slice, feature_slice, name=f"corr_{feature_name}")]
+
+
+def encode_metric_constructors() -> tp.List[tp.Callable[..., TestMetric]]:
+    """bm/solver.py:408-409, the encode task: the correlation of the predicted with the recorded MEG."""
+    return [OnlineCorrelation.get_constructor(slice(None), slice(None), "corr_meg")]
+
+
+def encode_trim_offset(sample_rate: float, tmin: float, meg_init: float) -> int:
+    """bm/solver.py:436-439: the samples the encode task's test metrics leave out IN FRONT of those the Solver already
+    removed (``_process_batch`` returns the samples after ``meg_init``): up to the stimulus onset at ``-tmin``."""
+    time_offset = -tmin
+    time_offset -= meg_init
+    return int(sample_rate * time_offset)
 
 
 def merge_rank_results(per_rank: tp.Sequence[tp.Dict[str, tp.List[torch.Tensor]]],

@@ -1,7 +1,7 @@
 """Host-side mirror of the hot loop of ``bm/solver.py``: ``_process_batch`` (bm/solver.py:230-321)
 and the per-batch body of ``_run_one_epoch`` (bm/solver.py:343-390), for the decode task with the
 CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80) or
-FeatureDecodingLoss (bm/solver.py:81-86).
+FeatureDecodingLoss (bm/solver.py:81-86), and for the encode task (bm/solver.py:287-293) with the L1 / MSE loss.
 Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
 construction) stays the reference's business.
 
@@ -22,6 +22,11 @@ from .losses import ClipLoss, FeatureDecodingLoss, _MaskedLoss
 from .optim import FlatAdam
 
 
+def encode_limit(meg_init: float, sample_rate: float) -> int:
+    """Samples of MEG the encode task shows the model (bm/solver.py:288, the reference's expression: same rounding)."""
+    return int(meg_init * sample_rate)
+
+
 class Solver:
     def __init__(self, model: torch.nn.Module, loss: tp.Optional[tp.Union[ClipLoss, _MaskedLoss, FeatureDecodingLoss]] = None,
                  optimizer: tp.Optional[FlatAdam] = None, device: str = "cuda",
@@ -29,7 +34,8 @@ class Solver:
                  lr: float = 3e-4, betas=(0.9, 0.999), scale_reject=None,
                  feature_model: tp.Optional[torch.nn.Module] = None, check_finite: bool = True,
                  n_negatives: tp.Optional[int] = None, negative_pool_size: tp.Optional[int] = None,
-                 batch_size: tp.Optional[int] = None, mask_loss: bool = False):
+                 batch_size: tp.Optional[int] = None, mask_loss: bool = False, task: str = "decode",
+                 meg_init: float = 0.3):
         """``batch_size``: the configured per-rank batch size (`optim.batch_size` / world size, bm/train.py:37-39).
         Only whole-node negatives next to per-rank rejection need it: it is the block every rank contributes to the
         candidate all-gather.  Without it the block is the local batch's length and is verified over the ranks each
@@ -40,8 +46,23 @@ class Solver:
         ``mask_loss`` (`task.mask_loss`, bm/solver.py:251-253) applies to the regression losses: False hands them
         ``mask=None`` (all true, what the reference's ``torch.ones_like`` means, without the tensor), True the batch's
         ``features_mask`` after the offset slice.  ClipLoss keeps receiving the batch's mask (it asserts it is all
-        true)."""
+        true).
+
+        ``task`` (`task.type`): "decode" (MEG -> features) or "encode" (bm/solver.py:287-293: the model gets the first
+        ``meg_init`` seconds of the MEG (`task.meg_init`) and the features, predicts the MEG, and the loss leaves out
+        those first samples).  The encode task takes ``L1Loss()`` / ``L2Loss()`` and nothing that belongs to the CLIP
+        candidates or to decoded features."""
         assert negatives in ("local", "node")
+        if task not in ("decode", "encode"):
+            raise ValueError(f"Unknown task {task!r}: 'decode' or 'encode'")     # bm/solver.py:295
+        self.task = task
+        self.meg_init = meg_init
+        if task == "encode":
+            if not isinstance(loss, _MaskedLoss):
+                raise ValueError('task="encode" predicts the MEG: it takes L1Loss() or L2Loss(), not '
+                                 f"{type(loss).__name__ if loss is not None else 'the default ClipLoss'}")
+            if feature_model is not None:
+                raise ValueError('task="encode": the target is the MEG, a feature_model has nothing to transform')
         self.regression = isinstance(loss, (_MaskedLoss, FeatureDecodingLoss))
         if self.regression:
             if n_negatives is not None:          # bm/solver.py:362: `assert self.args.optim.loss == 'clip'`
@@ -112,6 +133,7 @@ class Solver:
         self._flag_ring: tp.List[torch.Tensor] = []   # pinned host copies of the device flag word (see _post_flags)
         self._flag_i = 0
         self._flag_ticket = None
+        self._windows: tp.Dict[tuple, torch.Tensor] = {}      # (B, T, limit, device) -> bool [B, 1, T], t >= limit
 
     # -- bm/solver.py:243 `batch.to(self.device)` ----------------------------------------------------
     def stage(self, batch):
@@ -280,9 +302,12 @@ class Solver:
         otherwise only read by the next one.  ``eval_step``, ``predict`` and ``state_dict`` call it."""
         self._check_flags()
 
-    def _process_batch(self, batch, training: bool = False, defer_flags: bool = False):
-        """bm/solver.py:230-321.  ``defer_flags`` (train_step): the asserts are posted here and evaluated before the
-        backward pass (``_post_flags``); other callers get the reference's behaviour -- they raise before the model runs."""
+    def _forward(self, batch, training: bool = False, defer_flags: bool = False):
+        """bm/solver.py:230-297 and 304-320: (estimate, output, features_mask, reject_mask, limit) at FULL length --
+        the reference's slices ``[..., limit:]`` (bm/solver.py:299-302) are left to the caller: ``_process_batch`` takes
+        them as views, ``train_step`` / ``eval_step`` hand the loss the full tensors and a window mask instead.
+        ``defer_flags`` (train_step): the asserts are posted here and evaluated before the backward pass
+        (``_post_flags``); other callers get the reference's behaviour -- they raise before the model runs."""
         pre = self._prefetched
         self._prefetched = None
         if pre is not None and pre[0] is batch:
@@ -295,7 +320,7 @@ class Solver:
                 self._gather.cancel()                     # a prefetched gather nobody will consume
             prepared = self._prepare(batch)
         if prepared is None:
-            return None, None, None, None
+            return None, None, None, None, 0
         if defer_flags:
             # (a regression loss raises its "no mask!" bit in its own forward kernel: train_step posts the read behind it)
             if not self.regression:
@@ -303,20 +328,47 @@ class Solver:
         else:
             self._check_flags()
         batch, meg, features, features_mask, reject_mask = prepared
+        if self.task == "encode":
+            # bm/solver.py:287-293.  The target is the MEG itself: nothing writes to it, so no clone
+            limit = encode_limit(self.meg_init, self.sample_rate)
+            inputs = dict(meg=H.meg_init(meg, limit), features=features)
+            return self.model(inputs, batch), meg, features_mask, reject_mask, limit
         inputs = dict(meg=meg)
         estimate = self.model(inputs, batch)
         if self.feature_model is not None:
             features = self.feature_model(features)                   # bm/solver.py:304-320
-        return estimate, features, features_mask, reject_mask
+        return estimate, features, features_mask, reject_mask, 0
 
-    def _loss_mask(self, features_mask):
-        """The mask a regression loss gets: None (all true) unless ``mask_loss`` (bm/solver.py:251-253)."""
-        if not self.mask_loss:
+    def _process_batch(self, batch, training: bool = False, defer_flags: bool = False):
+        """bm/solver.py:230-321: (estimate, output, features_mask, reject_mask), for the encode task without their first
+        ``limit`` samples (views).  With ``limit`` 0 (the decode task) these are the very tensors ``_forward`` made: a
+        slice ``[..., 0:]`` would be a new tensor object without the maxima cached on the old one."""
+        estimate, output, features_mask, reject_mask, limit = self._forward(batch, training, defer_flags)
+        if estimate is None or not limit:
+            return estimate, output, features_mask, reject_mask
+        return estimate[..., limit:], output[..., limit:], features_mask[..., limit:], reject_mask
+
+    def _loss_mask(self, features_mask, limit: int = 0):
+        """The mask a regression loss gets for the full-length tensors: None (all true) unless ``mask_loss``
+        (bm/solver.py:251-253); with ``limit`` (the encode task) the window t >= limit, AND-ed with the batch's mask
+        under ``mask_loss`` -- the elements the reference selects from its slices ``[..., limit:]``."""
+        mask = features_mask if self.mask_loss else None
+        if limit:
+            B, _, T = features_mask.shape
+            key = (B, T, limit, features_mask.device)
+            window = self._windows.get(key)
+            if window is None:
+                if len(self._windows) >= 16:
+                    self._windows.clear()
+                window = (torch.arange(T, device=features_mask.device) >= limit).expand(B, 1, T).contiguous()
+                self._windows[key] = window
+            mask = window if mask is None else window & mask
+        if mask is None:
             return None
         if not self.check_finite:
             # no flag word to defer to: the reference's assert, synchronising (bm/solver.py:354-356)
-            assert bool(features_mask.any()), "no mask!"
-        return features_mask if features_mask.is_contiguous() else features_mask.contiguous()
+            assert bool(mask.any()), "no mask!"
+        return mask if mask.is_contiguous() else mask.contiguous()
 
     def _all_models(self):
         return [self.model] + ([self.feature_model] if self.feature_model is not None else [])
@@ -369,18 +421,18 @@ class Solver:
         # what the asserts of bm/solver.py:258-260 must leave untouched when they fire (the reference raises before it
         # touches any state; here they are evaluated after the forward pass, so that state is put back: `_rollback`)
         undo = self._snapshot()
-        estimate, output, features_mask, _ = self._process_batch(batch, training=True, defer_flags=True)
+        estimate, output, features_mask, _, limit = self._forward(batch, training=True, defer_flags=True)
         if estimate is None:
             # bm/solver.py:345-352: a fully rejected batch re-uses the last good one so that every
             # rank keeps issuing the same collectives
             if self._last_batch is None:
                 raise RuntimeError("Empty batch and last batch is none")
-            estimate, output, features_mask, _ = self._process_batch(self._last_batch, training=True,
-                                                                     defer_flags=True)
+            estimate, output, features_mask, _, limit = self._forward(self._last_batch, training=True,
+                                                                      defer_flags=True)
         elif not self._substituted:
             self._last_batch = batch
         if self.regression:
-            loss = self.loss(estimate, output, self._loss_mask(features_mask))
+            loss = self.loss(estimate, output, self._loss_mask(features_mask, limit))
             # the flag word now holds this batch's finiteness verdict AND the loss' "no mask!" bit
             self._flag_ticket = self._post_flags()
         else:
@@ -480,9 +532,9 @@ class Solver:
         for m in self._all_models():
             m.train(False)
         self.loss.train(False)
-        estimate, output, features_mask, _ = self._process_batch(batch, training=False)
+        estimate, output, features_mask, _, limit = self._forward(batch, training=False)
         if self.regression:
-            loss = self.loss(estimate, output, self._loss_mask(features_mask))
+            loss = self.loss(estimate, output, self._loss_mask(features_mask, limit))
         else:
             output, target_offset, valid = self._candidates(output)
             output = self._complete_with_pool(output, training=False)

@@ -361,6 +361,18 @@ int bm_regress_metric_update(const float* est, long est_bstride, const float* ou
                              const unsigned char* mask, long mask_bstride, int mask_full, int B, int F, int T, int t0,
                              double* acc, void* stream);
 
+/* ---- the encode task's model input (encode.hip)  bm/solver.py:288-292 ----
+ * meg, x: contiguous fp32 [B][C][T].  x[b][c][t] = meg[b][c][t] for t < limit and +0.0 for every other t: the
+ * reference's `mask * meg` with mask[:limit] = 1 (limit <= 0: all zeros; limit >= T: a copy).  ONE launch: only the
+ * head of meg is read, every element of x is written exactly once (no fill needed), 16-byte accesses when T % 4 == 0
+ * and both pointers are 16-byte aligned.  Unlike the product, a tail element is +0.0 where meg is negative and 0 where
+ * meg is not finite.  amax_out (nullable amax slot, compute mode f16x2) receives max |x|, folded by the workgroup that
+ * finishes last; it needs `workspace` (bm_meg_init_workspace_bytes: ticket counter + partial maxima), ZEROED by the
+ * caller once -- every launch leaves the counter at zero again.  B == 0 returns without a launch. */
+long bm_meg_init_workspace_bytes(void);
+int bm_meg_init(const float* meg, float* x, int B, int C, int T, int limit, float* amax_out, void* workspace,
+                long workspace_bytes, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip)  bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
