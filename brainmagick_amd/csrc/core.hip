@@ -20,7 +20,7 @@ int bm_check_launch(const char* what) {
 }
 
 extern "C" const char* bm_last_error(void) { return bm_err_buf; }
-extern "C" int bm_version(void) { return 109; }   // 0.1.9: the encode task's model input (bm_meg_init)
+extern "C" int bm_version(void) { return 110; }   // 0.1.10: task.lowpass (bm_lowpass)
 
 // Number of HIP devices visible; <0 on error.  Lets the Python side fail loudly early.
 extern "C" int bm_device_count(void) {

@@ -1055,7 +1055,118 @@ def meg_init(meg: torch.Tensor, limit: int) -> torch.Tensor:
     return x
 
 
-# FeatureDecodingLoss / ClassificationAcc (csrc/regress.hip).  ``table``: one row per feature, (kind, est_start, width,
+# task.lowpass (csrc/lowpass.hip): julius.lowpass_filter with stride 1 and pad=True.
+_lowpass_taps: tp.Dict[tp.Any, tp.Tuple[torch.Tensor, int]] = {}
+_lowpass_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
+
+
+def _check_cutoff(cutoff: float) -> None:
+    if cutoff < 0:
+        raise ValueError("Minimum cutoff must be larger than zero.")
+    if cutoff > 0.5:
+        raise ValueError("A cutoff above 0.5 does not make sense.")
+    if cutoff == 0:
+        raise ValueError("A cutoff of 0 is not a filter (julius would return a null signal).")
+
+
+def lowpass_taps(cutoff: float, zeros: float = 8, device=None) -> tp.Tuple[torch.Tensor, int]:
+    """(taps, half): the ``2 * half + 1`` fp32 coefficients of julius' ``LowPassFilter(cutoff, zeros=zeros)`` -- a
+    Hann-windowed sinc, normalised to a DC gain of 1 -- computed on the CPU with julius' own fp32 torch expressions, and
+    uploaded to ``device`` if one is given; cached per (cutoff, zeros, device).  ``cutoff`` is a fraction of the sample
+    rate in (0, 0.5]; julius raises ValueError outside [0, 0.5], and so does this, for 0 as well (julius then returns a
+    null signal: not a filter this project has a use for)."""
+    import math
+    _check_cutoff(cutoff)
+    device = torch.device(device) if device is not None else None
+    key = (float(cutoff), float(zeros), device)
+    hit = _lowpass_taps.get(key)
+    if hit is not None:
+        return hit
+    half = int(zeros / cutoff / 2)
+    time = torch.arange(-half, half + 1)
+    win = torch.hann_window(2 * half + 1, periodic=False)
+    arg = 2 * cutoff * math.pi * time
+    sinc = torch.where(arg == 0, 1., torch.sin(arg) / arg)
+    taps = 2 * cutoff * win * sinc
+    taps /= taps.sum()
+    assert taps.dtype == torch.float32 and taps.shape == (2 * half + 1,)
+    if device is not None:
+        taps = taps.to(device)
+    if len(_lowpass_taps) >= 64:
+        _lowpass_taps.clear()
+    _lowpass_taps[key] = (taps, half)
+    return taps, half
+
+
+def _lowpass_ws(device) -> torch.Tensor:
+    """Ticket counter + partial maxima of ``bm_lowpass``: one ZEROED buffer per (device, stream), as ``_encode_ws``."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _lowpass_workspaces.get(key)
+    if ws is None:
+        ws = _lowpass_workspaces[key] = torch.zeros(lib().bm_lowpass_workspace_bytes(), device=device,
+                                                    dtype=torch.uint8)
+    return ws
+
+
+def _uniform_rows(x: torch.Tensor) -> tp.Optional[int]:
+    """The distance in elements between consecutive rows of ``x`` seen as [rows, T] -- unit stride in the last
+    dimension, every leading dimension a whole number of the one behind it -- or None when ``x`` has no such form."""
+    T = x.shape[-1]
+    if T != 1 and x.stride(-1) != 1:
+        return None
+    lead = [(n, s) for n, s in zip(x.shape[:-1], x.stride()[:-1]) if n != 1]
+    if not lead:
+        return T
+    for (_, outer), (n, inner) in zip(lead[:-1], lead[1:]):
+        if outer != n * inner:
+            return None
+    row_stride = lead[-1][1]
+    return row_stride if row_stride >= T else None
+
+
+def lowpass_filter(x: torch.Tensor, cutoff: float, stride: int = 1, pad: bool = True, zeros: float = 8,
+                   fft: tp.Optional[bool] = None, keep: tp.Optional[int] = None,
+                   publish_amax: bool = True) -> torch.Tensor:
+    """``julius.lowpass_filter(x, cutoff, stride, pad, zeros, fft)`` over the last dimension (bm/solver.py:279 calls it
+    with ``zeros=5``) in one launch of ``bm_lowpass``: replicate padding, same length out, a new contiguous tensor of
+    ``x.shape``.  ``x``: fp32 on the GPU, any leading dimensions; a view whose rows are uniformly strided (``meg[...,
+    offset:]``) is read in place, anything else is made contiguous first.  ``keep``: only the samples t < keep are
+    computed, the others are +0.0 (the encode task's ``mask * lowpass(meg)``, bm/solver.py:288-292).
+
+    Against julius: the result is always the direct sum (fp32 fmaf, taps ascending), where julius switches to an FFT
+    convolution above 32 half-taps (``fft`` is accepted and ignored) -- the same mathematics, other last bits;
+    ``stride != 1`` and ``pad=False`` are not built.  In f16x2 mode with ``publish_amax`` the launch also publishes
+    max |y|: ``amax(y)`` costs no scan."""
+    if stride != 1:
+        raise NotImplementedError("lowpass_filter: stride != 1 (julius' decimating form) is not built")
+    if not pad:
+        raise NotImplementedError("lowpass_filter: pad=False (julius' valid convolution) is not built")
+    _check_cutoff(cutoff)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise BmHipError("lowpass_filter.x: expected a GPU tensor; the brainmagick_amd hot path has no CPU fallback "
+                         "(got %s)" % (x.device if isinstance(x, torch.Tensor) else type(x)))
+    if x.dtype != torch.float32:
+        raise BmHipError(f"lowpass_filter.x: expected dtype torch.float32, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise BmHipError(f"lowpass_filter: x {tuple(x.shape)} has no samples in its last dimension")
+    taps, half = lowpass_taps(cutoff, zeros, x.device)
+    T = x.shape[-1]
+    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    rows = y.numel() // T
+    if rows == 0:
+        return y
+    row_stride = _uniform_rows(x)
+    if row_stride is None:
+        x, row_stride = x.contiguous(), T
+    slot = _amax_slot(y) if publish_amax else None
+    ws = _lowpass_ws(x.device) if slot is not None else None
+    check(lib().bm_lowpass(_p(x), row_stride, _p(y), rows, T, T if keep is None else max(0, min(int(keep), T)),
+                           _p(taps), half, _p(slot), _p(ws), ws.numel() if ws is not None else 0, _stream()),
+          "bm_lowpass")
+    return y
+
+
+# FeatureDecodingLoss / ClassificationAcc (csrc/regress.hip). ``table``: one row per feature, (kind, est_start, width,
 # out_start, weight_off) with kind 0 = continuous, 1 = categorical (width = number of classes) and weight_off the
 # feature's offset into ``weights`` or -1.
 FEATURE_CONTINUOUS, FEATURE_CATEGORICAL = 0, 1

@@ -1,7 +1,8 @@
 """Host-side mirror of the hot loop of ``bm/solver.py``: ``_process_batch`` (bm/solver.py:230-321)
 and the per-batch body of ``_run_one_epoch`` (bm/solver.py:343-390), for the decode task with the
 CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80) or
-FeatureDecodingLoss (bm/solver.py:81-86), and for the encode task (bm/solver.py:287-293) with the L1 / MSE loss.
+FeatureDecodingLoss (bm/solver.py:81-86), and for the encode task (bm/solver.py:287-293) with the L1 / MSE loss; both
+with the optional low-pass filter of the MEG (`task.lowpass`, bm/solver.py:278-281).
 Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
 construction) stays the reference's business.
 
@@ -35,7 +36,7 @@ class Solver:
                  feature_model: tp.Optional[torch.nn.Module] = None, check_finite: bool = True,
                  n_negatives: tp.Optional[int] = None, negative_pool_size: tp.Optional[int] = None,
                  batch_size: tp.Optional[int] = None, mask_loss: bool = False, task: str = "decode",
-                 meg_init: float = 0.3):
+                 meg_init: float = 0.3, lowpass: float = 0., lowpass_gt: bool = True, lowpass_gt_test: bool = False):
         """``batch_size``: the configured per-rank batch size (`optim.batch_size` / world size, bm/train.py:37-39).
         Only whole-node negatives next to per-rank rejection need it: it is the block every rank contributes to the
         candidate all-gather.  Without it the block is the local batch's length and is verified over the ranks each
@@ -51,8 +52,20 @@ class Solver:
         ``task`` (`task.type`): "decode" (MEG -> features) or "encode" (bm/solver.py:287-293: the model gets the first
         ``meg_init`` seconds of the MEG (`task.meg_init`) and the features, predicts the MEG, and the loss leaves out
         those first samples).  The encode task takes ``L1Loss()`` / ``L2Loss()`` and nothing that belongs to the CLIP
-        candidates or to decoded features."""
+        candidates or to decoded features.
+
+        ``lowpass`` (`task.lowpass`, Hz; 0 = off, bm/solver.py:278-281): the MEG is low-pass filtered after the offset
+        slice (``hip_ops.lowpass_filter``, julius' filter with ``zeros=5``, one launch that reads the offset view in
+        place).  It is the model's input in either task.  The encode task's target is the filtered MEG when
+        ``(lowpass_gt and training) or lowpass_gt_test`` (`task.lowpass_gt`, `task.lowpass_gt_test`: the reference's
+        expression, so ``lowpass_gt_test`` acts in training too), else the unfiltered one."""
         assert negatives in ("local", "node")
+        if lowpass < 0 or lowpass > sample_rate / 2:
+            raise ValueError(f"lowpass = {lowpass} Hz: the cutoff lies between 0 (off) and half the sample rate "
+                             f"({sample_rate / 2} Hz)")
+        self.lowpass = lowpass
+        self.lowpass_gt = lowpass_gt
+        self.lowpass_gt_test = lowpass_gt_test
         if task not in ("decode", "encode"):
             raise ValueError(f"Unknown task {task!r}: 'decode' or 'encode'")     # bm/solver.py:295
         self.task = task
@@ -223,7 +236,8 @@ class Solver:
                                    verify_block=self.batch_size is None)
             else:
                 self._gather.start(features)
-        return batch, meg.contiguous(), features, features_mask, reject_mask
+        # (with task.lowpass the filter reads the offset view in place: no copy)
+        return batch, meg if self.lowpass else meg.contiguous(), features, features_mask, reject_mask
 
     def prefetch(self, next_batch) -> None:
         """Optional: hand over the batch of the NEXT step (``train_step(batch, next_batch=...)`` calls this between
@@ -331,8 +345,21 @@ class Solver:
         if self.task == "encode":
             # bm/solver.py:287-293.  The target is the MEG itself: nothing writes to it, so no clone
             limit = encode_limit(self.meg_init, self.sample_rate)
-            inputs = dict(meg=H.meg_init(meg, limit), features=features)
+            if not self.lowpass:
+                inputs = dict(meg=H.meg_init(meg, limit), features=features)
+            elif (self.lowpass_gt and training) or self.lowpass_gt_test:         # bm/solver.py:280
+                # the filtered MEG is the target too: filter at full length (nobody contracts the target: no maximum)
+                meg = H.lowpass_filter(meg, self.lowpass / self.sample_rate, zeros=5, publish_amax=False)
+                inputs = dict(meg=H.meg_init(meg, limit), features=features)
+            else:
+                # mask * lowpass(meg) in one launch that computes the head only; the target is the unfiltered MEG
+                inputs = dict(meg=H.lowpass_filter(meg, self.lowpass / self.sample_rate, zeros=5, keep=limit),
+                              features=features)
+                meg = meg.contiguous()
             return self.model(inputs, batch), meg, features_mask, reject_mask, limit
+        if self.lowpass:
+            # bm/solver.py:279: the filter's launch replaces the copy of the offset view and publishes max |meg|
+            meg = H.lowpass_filter(meg, self.lowpass / self.sample_rate, zeros=5)
         inputs = dict(meg=meg)
         estimate = self.model(inputs, batch)
         if self.feature_model is not None:

@@ -373,7 +373,25 @@ long bm_meg_init_workspace_bytes(void);
 int bm_meg_init(const float* meg, float* x, int B, int C, int T, int limit, float* amax_out, void* workspace,
                 long workspace_bytes, void* stream);
 
-/* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip)  bm/losses.py:117-173, bm/metrics.py:173-180 ----
+/* ---- task.lowpass (lowpass.hip)  bm/solver.py:278-281 ----
+ * julius.lowpass_filter(x, cutoff, zeros) with stride 1 and pad=True as one launch: a FIR of 2 * half + 1 taps over the
+ * replicate-padded rows,  y[r][t] = sum_k taps[k] * x[r][clamp(t + k - half, 0, T - 1)]  for t < keep and +0.0 for
+ * t >= keep (keep saturates to [0, T]; keep < T is the encode task's `mask * lowpass(meg)`, which reads only
+ * x[r][0 : min(T, keep + half)] and, like bm_meg_init, gives +0.0 in the tail whatever x holds there).
+ * x: `rows` rows of T fp32 samples, unit stride inside a row, row_stride >= T floats between rows (a view
+ * meg[..., offset:] is read in place); nothing outside [row start, row start + T) is read.  y: contiguous [rows][T],
+ * every element written exactly once.  taps: 2 * half + 1 floats on the device.  The sum is always the direct one, fp32
+ * fmaf with k ascending from 0.f: the scalar and the 16-byte paths (loads: x and row_stride 16-byte aligned; stores:
+ * T % 4 == 0 and y aligned), every grid and every keep give the same bits.  T + 2 * half <= 8192 (the padded row is
+ * staged in LDS), else BM_ERR_UNSUPPORTED; rows * T < 2^31.  amax_out (nullable amax slot, compute mode f16x2) receives
+ * max |y|, folded by the workgroup that finishes last; it needs `workspace` (bm_lowpass_workspace_bytes: ticket counter
+ * + partial maxima), ZEROED by the caller once -- every launch leaves the counter at zero again.  rows == 0 returns
+ * without a launch. */
+long bm_lowpass_workspace_bytes(void);
+int bm_lowpass(const float* x, long row_stride, float* y, int rows, int T, int keep, const float* taps, int half,
+               float* amax_out, void* workspace, long workspace_bytes, void* stream);
+
+/* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
  * (width channels of est and of out, MSE over the selected positions and those channels), 1 = categorical (width = K
