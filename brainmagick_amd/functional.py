@@ -680,3 +680,30 @@ class LSTMFn(torch.autograd.Function):
             dy = dx
         dxo = _c(dy.permute(2, 1, 0)) if ctx.needs_input_grad[0] else None
         return (dxo, None, None, None, None, None) + tuple(grads)
+
+
+class SpectralPenaltyFn(torch.autograd.Function):
+    """``apply(R_all, niters, *weights)`` -> the sum over the weights of ``torch.svd_lowrank(w.view(w.shape[0], -1),
+    dim, niters)[1][0] ** 2`` (bm/svd.py:40-45) computed with the test matrices ``R_all`` [sum of min(rows, cols), dim]
+    in place of svd_lowrank's own draw; all weights in the same launches (csrc/spectral.hip).  (``niters`` has to reach
+    the kernels: it is an argument in front of the weights.)  The backward is the closed-form gradient of that estimate
+    -- the dependence of the orthonormal bases on the weight included, no autograd through a QR -- scaled by the incoming
+    gradient; every gradient is a fresh tensor (never a view of an optimizer's bucket: autograd accumulates it with
+    what the convolution kernels wrote there), and ``R_all`` gets none."""
+
+    @staticmethod
+    def forward(ctx, R_all, niters, *weights):
+        # (read in place: a weight that is not contiguous is refused, as the reference's `p.view` refuses it)
+        plan = H.spectral_plan([w.detach() for w in weights], R_all.shape[1], niters)
+        total, _ = H.spectral_fwd(plan, R_all)
+        ctx.plan, ctx.generation, ctx.R = plan, plan.generation, R_all
+        return total
+
+    @staticmethod
+    def backward(ctx, dtotal):
+        plan = ctx.plan
+        if plan.generation != ctx.generation:
+            H.spectral_fwd(plan, ctx.R)          # another forward used the workspaces since: put this one's bases back
+            ctx.generation = plan.generation
+        grads = H.spectral_bwd(plan, _c(dtotal.to(torch.float32)).view(1))
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))

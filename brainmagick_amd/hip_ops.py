@@ -1515,3 +1515,105 @@ def lstm_layer_bwd(whh: tp.Sequence[torch.Tensor], dy: torch.Tensor, gates: torc
                                       Hd, B, T, dirs, _stream()), "bm_lstm_layer_bwd")
     _timed(f"lstm_step_bwd_kernel<dirs={dirs}>", 2.0 * T * dirs * H4 * Hd * B, launch)
     return dg
+
+
+# ------------------------------------------------------------------------------------------------
+# optim.svd (csrc/spectral.hip, bm/svd.py:17-45): the low-rank estimate of every weight's largest singular value, squared,
+# and its closed-form gradient -- all matrices of a model in the same launches.  Exact-fp32 MFMA in every compute mode.
+SPECTRAL_MAX_DIM = 16
+SPECTRAL_MAX_NITERS = 8
+
+
+def spectral_check_limits(dim: int, niters: int) -> None:
+    if not 1 <= dim <= SPECTRAL_MAX_DIM:
+        raise ValueError(f"svd_penalty: dim = {dim}, the kernels take 1..{SPECTRAL_MAX_DIM} (the projection is one "
+                         f"{SPECTRAL_MAX_DIM}-wide MFMA operand)")
+    if not 0 <= niters <= SPECTRAL_MAX_NITERS:
+        raise ValueError(f"svd_penalty: niters = {niters}, the kernels take 0..{SPECTRAL_MAX_NITERS}")
+
+
+class SpectralPlan:
+    """The device table of ``bm_spectral_*`` for one list of weights (viewed as ``p.view(p.shape[0], -1)``, read in
+    place) and the two workspaces.  ``sizes[i]`` = min(rows, cols): the rows matrix i takes of the test matrix R.
+    ``generation`` counts the forward passes: the backward needs the workspaces as ITS forward left them."""
+
+    def __init__(self, weights: tp.Sequence[torch.Tensor], dim: int, niters: int):
+        spectral_check_limits(dim, niters)
+        L = lib()
+        self.dim, self.niters, self.nmat = dim, niters, len(weights)
+        self.device = weights[0].device
+        self.shapes = [tuple(w.shape) for w in weights]
+        entry = L.bm_spectral_table_entry_bytes()
+        host = torch.zeros(self.nmat, entry, dtype=torch.uint8)
+        self.sizes, self.grad_offsets = [], []
+        wsf = wsd = r_off = g_off = 0
+        self.max_slabs = self.max_tiles = 1
+        for i, w in enumerate(weights):
+            _req(w, "spectral.weight")
+            if w.dim() < 2 or w.numel() == 0 or w.device != self.device:
+                raise BmHipError(f"spectral: weight {i} of shape {tuple(w.shape)} on {w.device} is no matrix of this plan")
+            rows, cols = w.shape[0], w.numel() // w.shape[0]
+            check(L.bm_spectral_table_fill(ctypes.c_void_p(host[i].data_ptr()), _p(w), rows, cols, cols, dim, r_off, wsf,
+                                           wsd, g_off), "bm_spectral_table_fill")
+            self.sizes.append(min(rows, cols))
+            self.grad_offsets.append(g_off)
+            r_off += min(rows, cols)
+            g_off += rows * cols
+            wsf += L.bm_spectral_ws_floats(rows, cols, niters)
+            wsd += L.bm_spectral_ws_doubles(rows, cols, niters)
+            self.max_slabs = max(self.max_slabs, -(-max(rows, cols) // 64))
+            self.max_tiles = max(self.max_tiles, -(-rows // 64) * -(-cols // 64))
+        self.r_rows, self.grad_numel = r_off, g_off
+        self.table = host.to(self.device)
+        self.ws_floats = torch.empty(wsf, device=self.device, dtype=torch.float32)
+        self.ws_doubles = torch.empty(wsd, device=self.device, dtype=torch.float64)
+        self.generation = 0
+
+
+_spectral_plans: tp.Dict[tuple, SpectralPlan] = {}
+
+
+def spectral_plan(weights: tp.Sequence[torch.Tensor], dim: int, niters: int) -> SpectralPlan:
+    """The plan of these weights, kept while their addresses and shapes stay (a model's parameters do)."""
+    for w in weights:
+        _req(w, "spectral.weight")
+    key = (tuple((w.data_ptr(), tuple(w.shape)) for w in weights), dim, niters, weights[0].device,
+           torch.cuda.current_stream(weights[0].device).cuda_stream)
+    plan = _spectral_plans.get(key)
+    if plan is None:
+        if len(_spectral_plans) >= 8:
+            _spectral_plans.clear()
+        plan = _spectral_plans[key] = SpectralPlan(weights, dim, niters)
+    return plan
+
+
+def spectral_fwd(plan: SpectralPlan, R: torch.Tensor) -> tp.Tuple[torch.Tensor, torch.Tensor]:
+    """R [sum of min(rows, cols), dim] -> (sum of the estimates (0-dim), the estimates [nmat])."""
+    _req(R, "spectral_fwd.R")
+    if tuple(R.shape) != (plan.r_rows, plan.dim):
+        raise BmHipError(f"spectral_fwd: R is {tuple(R.shape)}, these weights need {(plan.r_rows, plan.dim)}")
+    values = torch.empty(plan.nmat, device=plan.device, dtype=torch.float32)
+    total = torch.empty((), device=plan.device, dtype=torch.float32)
+    plan.generation += 1
+
+    def launch():
+        check(lib().bm_spectral_fwd(_p(plan.table), plan.nmat, plan.max_slabs, _p(R), plan.dim, plan.niters,
+                                    _p(plan.ws_floats), _p(plan.ws_doubles), _p(values), _p(total), _stream()),
+              "bm_spectral_fwd")
+    _timed("spectral_fwd", 0., launch)
+    return total, values
+
+
+def spectral_bwd(plan: SpectralPlan, gscale: torch.Tensor) -> tp.List[torch.Tensor]:
+    """After ``spectral_fwd`` on the same plan: ``gscale`` (one fp32 element on the device) times the gradient of every
+    estimate, as fresh tensors of the weights' shapes (views of one new buffer)."""
+    _req(gscale, "spectral_bwd.gscale")
+    assert gscale.numel() == 1
+    flat = torch.empty(plan.grad_numel, device=plan.device, dtype=torch.float32)
+
+    def launch():
+        check(lib().bm_spectral_bwd(_p(plan.table), plan.nmat, plan.max_slabs, plan.max_tiles, plan.niters,
+                                    _p(plan.ws_floats), _p(plan.ws_doubles), _p(gscale), _p(flat), _stream()),
+              "bm_spectral_bwd")
+    _timed("spectral_bwd", 0., launch)
+    return [flat[off:off + torch.Size(shape).numel()].view(shape) for off, shape in zip(plan.grad_offsets, plan.shapes)]

@@ -2,7 +2,8 @@
 and the per-batch body of ``_run_one_epoch`` (bm/solver.py:343-390), for the decode task with the
 CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm/solver.py:76-80) or
 FeatureDecodingLoss (bm/solver.py:81-86), and for the encode task (bm/solver.py:287-293) with the L1 / MSE loss; both
-with the optional low-pass filter of the MEG (`task.lowpass`, bm/solver.py:278-281).
+with the optional low-pass filter of the MEG (`task.lowpass`, bm/solver.py:278-281) and the optional spectral penalty on
+the model's weights (`optim.svd`, bm/solver.py:379-380).
 Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
 construction) stays the reference's business.
 
@@ -36,7 +37,8 @@ class Solver:
                  feature_model: tp.Optional[torch.nn.Module] = None, check_finite: bool = True,
                  n_negatives: tp.Optional[int] = None, negative_pool_size: tp.Optional[int] = None,
                  batch_size: tp.Optional[int] = None, mask_loss: bool = False, task: str = "decode",
-                 meg_init: float = 0.3, lowpass: float = 0., lowpass_gt: bool = True, lowpass_gt_test: bool = False):
+                 meg_init: float = 0.3, lowpass: float = 0., lowpass_gt: bool = True, lowpass_gt_test: bool = False,
+                 svd: float = 0.):
         """``batch_size``: the configured per-rank batch size (`optim.batch_size` / world size, bm/train.py:37-39).
         Only whole-node negatives next to per-rank rejection need it: it is the block every rank contributes to the
         candidate all-gather.  Without it the block is the local batch's length and is verified over the ranks each
@@ -58,8 +60,17 @@ class Solver:
         slice (``hip_ops.lowpass_filter``, julius' filter with ``zeros=5``, one launch that reads the offset view in
         place).  It is the model's input in either task.  The encode task's target is the filtered MEG when
         ``(lowpass_gt and training) or lowpass_gt_test`` (`task.lowpass_gt`, `task.lowpass_gt_test`: the reference's
-        expression, so ``lowpass_gt_test`` acts in training too), else the unfiltered one."""
+        expression, so ``lowpass_gt_test`` acts in training too), else the unfiltered one.
+
+        ``svd`` (`optim.svd`, bm/solver.py:379-380; 0 = off): the weight of ``svd.svd_penalty(self.model)``, the squared
+        largest singular value of every conv / linear weight of the model (not of the feature model or the loss),
+        added to the training loss.  ``svd_test_matrices`` (an attribute; None, or an iterator of lists) hands each
+        step's penalty its test matrices instead of a draw from the device generator: tests pin the result with it."""
         assert negatives in ("local", "node")
+        if svd < 0:
+            raise ValueError(f"svd = {svd}: the weight of the spectral penalty is 0 (off) or positive")
+        self.svd = svd
+        self.svd_test_matrices: tp.Optional[tp.Iterator[tp.List[torch.Tensor]]] = None
         if lowpass < 0 or lowpass > sample_rate / 2:
             raise ValueError(f"lowpass = {lowpass} Hz: the cutoff lies between 0 (off) and half the sample rate "
                              f"({sample_rate / 2} Hz)")
@@ -469,8 +480,8 @@ class Solver:
                              **self._gathered_estimates(estimate))
         if next_batch is not None:
             self.prefetch(next_batch)       # the next step's candidate all-gather runs next to this backward
-        # bm/solver.py:375-380: `training_penalty` of every module that has one (ChannelMerger with merger_penalty:
-        # a constant, see models/common.py); optim.svd defaults to 0 and stays with the reference
+        # bm/solver.py:375-378: `training_penalty` of every module that has one (ChannelMerger with merger_penalty:
+        # a constant, see models/common.py)
         for mod in self.model.modules():
             if hasattr(mod, "training_penalty"):
                 loss = loss + mod.training_penalty.to(loss.device)
@@ -481,6 +492,12 @@ class Solver:
         except (AssertionError, IndexError):
             self._rollback(undo)
             raise
+        if self.svd:
+            # bm/solver.py:379-380, behind the asserts: a step that is rolled back has drawn nothing from the device
+            # generator and launched nothing of the penalty
+            from .svd import svd_penalty
+            matrices = next(self.svd_test_matrices) if self.svd_test_matrices is not None else None
+            loss = loss + self.svd * svd_penalty(self.model, test_matrices=matrices)
         self.optimizer.zero_grad(set_to_none=True)
         with self.optimizer.writing_grads():       # the weight-gradient kernels write straight into the flat bucket
             loss.backward()

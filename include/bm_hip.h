@@ -391,6 +391,32 @@ long bm_lowpass_workspace_bytes(void);
 int bm_lowpass(const float* x, long row_stride, float* y, int rows, int T, int keep, const float* taps, int half,
                float* amax_out, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- optim.svd (spectral.hip)  bm/svd.py:17-45, bm/solver.py:379-380 ----
+ * svd_penalty: for every penalised weight A = p.view(p.shape[0], -1) (bm/svd.py:40) the estimate
+ * torch.svd_lowrank(A, dim, niters)[1][0] ** 2 (bm/svd.py:44) and its gradient in closed form, all matrices of a model
+ * in the same launches.  A table entry (bm_spectral_table_entry_bytes bytes, filled on the host by
+ * bm_spectral_table_fill, then copied to the device) describes one matrix: `w` rows x cols fp32 read in place with
+ * `ld` floats between rows, `r_off` the first of its min(rows, cols) rows in the Gaussian test matrix R [sum, dim]
+ * (of which the first min(dim, rows, cols) columns are used), its offsets into the two workspaces (floats: a multiple
+ * of 16; sizes from bm_spectral_ws_floats / _doubles) and into the flat gradient buffer.  dim 1..16, niters 0..8.
+ * bm_spectral_fwd: 2 niters + 2 stage launches over a (64-row slab, matrix) grid (max_slabs: the largest
+ * cdiv(max(rows, cols), 64)), one Jacobi launch, one that adds the estimates: values[nmat], *total.  The products are
+ * exact-fp32 MFMA in every compute mode; the 16 x 16 Gram matrices, their Cholesky factors and the eigenpair are fp64.
+ * bm_spectral_bwd (after bm_spectral_fwd on the same workspaces, which carry the forward's bases): 2 niters + 2
+ * launches of the same kernel and one (max_tiles: the largest cdiv(rows, 64) * cdiv(cols, 64)) that writes
+ * grads[g_off + r * cols + c] = *gscale * d value / d A[r][c], every element once.  Stream order is the only
+ * synchronisation, no atomics: the same bits every run.  The workspaces need no initialisation and hold no state
+ * between calls.  nmat == 0 returns without a launch. */
+long bm_spectral_table_entry_bytes(void);
+long bm_spectral_ws_floats(int rows, int cols, int niters);
+long bm_spectral_ws_doubles(int rows, int cols, int niters);
+int bm_spectral_table_fill(void* entry, const float* w, int rows, int cols, long ld, int dim, long r_off,
+                           long ws_float_off, long ws_double_off, long grad_off);
+int bm_spectral_fwd(const void* table, int nmat, int max_slabs, const float* R, int dim, int niters,
+                    float* ws_floats, double* ws_doubles, float* values, float* total, void* stream);
+int bm_spectral_bwd(const void* table, int nmat, int max_slabs, int max_tiles, int niters, float* ws_floats,
+                    double* ws_doubles, const float* gscale, float* grads, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
