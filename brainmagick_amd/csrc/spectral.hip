@@ -6,7 +6,8 @@
 // With q = min(dim, nt) columns of the Gaussian test matrix R and S = 2 niters + 2 stages, M_k = At (k even) / At^T (k odd):
 //     X_k = M_k Q_{k-1}   (Q_{-1} = R),     Q_k = X_k L_k^{-T},   L_k L_k^T = X_k^T X_k   (Cholesky of the fp64 Gram matrix)
 //     value = largest eigenvalue of X_{S-1}^T X_{S-1}   (X_{S-1}^T = B = Q^T At),  eigenvector u.
-// The value depends on range(Q_k) only, so any orthonormalisation gives torch's number.  A Gram matrix accumulated in fp32
+// The value depends on range(Q_k) only, so any orthonormalisation gives torch's number -- a column of X_k that adds nothing
+// to the range is dropped (sp_chol_inv), so a rank-deficient X_k keeps its range too.  A Gram matrix accumulated in fp32
 // loses a decaying spectrum (sigma_16 / sigma_1 = 3e-5 squares to 1e-9): the Gram partials, the factorisation, L^{-1} and
 // the product X L^{-T} are fp64; what is stored (X, Q) is fp32.
 //
@@ -110,23 +111,44 @@ __device__ __forceinline__ double* sp_eig(double* wsd, const SpMat& m, int S) {
 
 // Ls: a symmetric 16 x 16 matrix whose leading q x q block is factorised in place (lower L); Li receives L^{-1}, zero
 // outside the block.  All SP_THREADS threads call it.
+//
+// A pivot that carries no information DROPS its column: row and column j of L^{-1} are zero, there is no rank-1 update,
+// so Q gets a zero column and range(Q) stays range(X) -- what Householder QR gives torch at a rank-deficient X (a zero or
+// duplicated column of a weight with at most 16 of them, a weight of rank below 16, the all-zero weight), where a plain
+// Cholesky takes the root of a rounding residue of either sign and ends in NaN.  The pivot d_j is the squared distance of
+// column j of X from the span of the columns before it.  X is STORED in fp32: each element carries a relative error of
+// up to eps = 2^-24, a column of squared norm g an error of squared norm up to eps^2 g, and the distance sees the errors
+// of at most SP_Q columns, none of them longer than dmax = the largest diagonal entry of the Gram matrix.  A pivot of at
+// most SP_Q eps^2 dmax (5.7e-14 dmax) is therefore what rounding alone can put there.  What the fixture factors is far
+// above it (its worst case, spectrum 0.5^i, has pivots from 1e-9 dmax).  The comparison is false for a NaN pivot: a NaN
+// weight still ends in a NaN value.
+#define SP_PIVOT_FLOOR (16.0 * 0x1p-48)             // SP_Q eps^2
 __device__ __forceinline__ void sp_chol_inv(double* Ls, double* Li, int q) {
     const int t = threadIdx.x, i = t >> 4, c = t & 15;
+    __syncthreads();
+    double dmax = 0.0;
+    for (int j = 0; j < q; ++j) {
+        const double g = Ls[j * 16 + j];
+        if (g > dmax) dmax = g;
+    }
+    unsigned dropped = 0;                           // uniform: every thread sees the same pivots
     for (int j = 0; j < q; ++j) {
         __syncthreads();
         const double d = Ls[j * 16 + j], lij = Ls[i * 16 + j], lcj = Ls[c * 16 + j];
         __syncthreads();
+        const bool drop = d <= SP_PIVOT_FLOOR * dmax;
+        if (drop) dropped |= 1u << j;
         if (i < q && c < q) {
             if (c == j) {
-                if (i >= j) Ls[i * 16 + j] = i == j ? sqrt(d) : lij / sqrt(d);
-            } else if (c > j && i >= c) {
+                if (i >= j) Ls[i * 16 + j] = drop ? (i == j ? 1.0 : 0.0) : (i == j ? sqrt(d) : lij / sqrt(d));
+            } else if (c > j && i >= c && !drop) {
                 Ls[i * 16 + c] -= lij * lcj / d;
             }
         }
     }
     Li[t] = 0.0;
     __syncthreads();
-    if (t < q) {                                    // column t of L^{-1} by forward substitution
+    if (t < q && !(dropped >> t & 1)) {             // column t of L^{-1} by forward substitution
         double x[SP_Q];
 #pragma unroll
         for (int r = 0; r < SP_Q; ++r) {
@@ -135,7 +157,7 @@ __device__ __forceinline__ void sp_chol_inv(double* Ls, double* Li, int q) {
                 double s = r == t ? 1.0 : 0.0;
 #pragma unroll
                 for (int j = 0; j < r; ++j) s -= Ls[r * 16 + j] * x[j];
-                x[r] = r >= t ? s / Ls[r * 16 + r] : 0.0;
+                x[r] = r >= t && !(dropped >> r & 1) ? s / Ls[r * 16 + r] : 0.0;
                 Li[r * 16 + t] = x[r];
             }
         }

@@ -5,7 +5,12 @@ Differences to the reference:
   * the Gaussian test matrices of all penalised weights are ONE ``torch.randn`` draw per call (the reference draws one per
     weight inside ``torch.svd_lowrank``): the same distribution, another stream;
   * ``test_matrices`` replaces the draw (tests and fixtures pin the result with it), ``generator`` seeds it;
-  * ``exact=True`` (a full SVD, "slow but useful at validation") and ``dim > 16`` are not built.
+  * ``exact=True`` (a full SVD, "slow but useful at validation") and ``dim > 16`` are not built;
+  * at a weight whose basis is rank deficient (a zero or duplicated column or row with ``min(rows, cols) <= 16``, rank
+    below 16) the value is the reference's, and the gradient is the finite ``2 sigma_1 u_1 v_1^T`` where the reference's
+    QR backward divides by a zero or rounding-noise pivot (its fp32 gradient is off by up to 0.5 in relative norm
+    at rank 1 and by 1e9 .. 1e21 at an exactly singular basis);
+  * at the all-zero weight value and gradient are exactly 0, where the reference returns 0 and a NaN gradient.
 """
 import random
 import typing as tp

@@ -2,7 +2,8 @@
 bookkeeping, the guards of ``svd_penalty`` and of the Solver, the entry points, the stage kernel's scratch budget -- and
 the closed-form gradient itself: an fp64 torch restatement of what ``csrc/spectral.hip`` computes (Cholesky-orthonormalised
 bases, the backward chain of skinny products and triangular solves, the sum of rank-16 terms) against the reference's
-fp64 value and autograd gradient."""
+fp64 value and autograd gradient.  At the end, the proofs of tests/svd_cases.py, the harness of
+tests/test_svd_conditioning_gpu.py."""
 import ctypes
 import inspect
 import json
@@ -25,6 +26,7 @@ import make_svd_golden as G  # noqa: E402
 import make_lowpass_golden as LPG  # noqa: E402
 
 from helpers import tensor_digest  # noqa: E402
+import svd_cases as SC  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -313,3 +315,63 @@ def test_spectral_kernels_use_no_scratch():
     scratch = [int(l.split(":")[1]) for l in text.splitlines() if ".private_segment_fixed_size" in l]
     assert len(spills) == 8 and len(scratch) == 4
     assert all(s == 0 for s in spills) and all(s == 0 for s in scratch), (spills, scratch)
+
+
+# ---- the harness of tests/test_svd_conditioning_gpu.py (tests/svd_cases.py), proven without a GPU -----------------------------
+@pytest.mark.parametrize("name", ["gauss_150x70", "gauss_70x150"])
+def test_lowrank_ref_is_torch_svd_lowrank_with_its_draw_given(name):
+    """``svd_cases.lowrank_ref`` against ``torch.svd_lowrank`` itself in fp64, fed the same R through the tap the
+    fixture's generator uses: 1e-12 relative (measured 1.5e-15), one tall and one wide matrix."""
+    w, R, niters = SC.shape_case(name)
+    with G.RandnTap(replay=[R]) as tap:
+        want = torch.svd_lowrank(w.double(), SC.DIM, niters)[1][0] ** 2
+    assert len(tap.seen) == 1
+    got, _ = SC.lowrank_ref(w.double(), R, niters, want_grad=False)
+    err = abs(float(got) - float(want)) / float(want)
+    print(f"{name}: lowrank_ref against torch.svd_lowrank {err:.2e}")
+    assert err <= 1e-12, (name, err)
+
+
+@pytest.mark.parametrize("name", list(SC.SHAPES))
+def test_shape_cases_keep_the_yardstick_meaningful(name):
+    """The tolerance of a shape case is a multiple of its own fp32-vs-fp64 deviation of the reference: that deviation
+    is capped, so a seed at which the reference itself is badly off cannot make the GPU test vacuous."""
+    _, g64, dev = SC.shape_truth(name)
+    cap = SC.GRAD_DEV_CAP * SC.dev_median()[1]
+    print(f"{name}: reference fp32-vs-fp64 value {dev[0]:.2e}, gradient {dev[1]:.2e} / cap {cap:.2e}")
+    assert bool(torch.isfinite(g64).all())
+    assert dev[1] <= cap, (name, dev, cap)
+
+
+@pytest.mark.parametrize("name", list(SC.LADDER))
+def test_the_analytic_truth_is_the_estimate_s_on_the_ladder(name):
+    """The condition for holding the kernels to ``sigma_1 ** 2`` and ``2 sigma_1 u v^T``: the reference's algorithm in
+    fp64 gives them, value and autograd gradient, to 1e-9 (measured 2e-14 or better).  A case that fails this is
+    replaced, not loosened."""
+    w, R, niters = SC.ladder_case(name)
+    value, grad, _ = SC.ladder_truth(name)
+    v64, g64 = SC.lowrank_ref(w.double(), R, niters)
+    err_v, err_g = abs(float(v64) - float(value)) / float(value), SC.rel(g64, grad)
+    print(f"{name}: fp64 lowrank_ref against the analytic truth: value {err_v:.2e}, gradient {err_g:.2e}")
+    assert err_v <= 1e-9 and err_g <= 1e-9, (name, err_v, err_g)
+
+
+@pytest.mark.parametrize("name", list(SC.SINGULAR))
+def test_the_analytic_truth_is_the_estimate_s_at_a_singular_gram_matrix(name):
+    """With min(rows, cols) <= 16 the basis spans the whole row space: the reference's fp64 VALUE is ``sigma_1 ** 2`` to
+    1e-9 (measured 2e-15).  Its autograd gradient divides by the zero pivot of R and is no truth; that the analytic one is
+    the gradient of that value is shown by the value itself, as a central difference along a random direction."""
+    w, R, niters = SC.ladder_case(name)
+    value, grad, _ = SC.ladder_truth(name)
+    v64, _ = SC.lowrank_ref(w.double(), R, niters, want_grad=False)
+    err_v = abs(float(v64) - float(value)) / float(value)
+    D = torch.randn(w.shape, generator=SC.gen(name + "/direction"), dtype=torch.float64)
+    D = D / D.norm()
+    h = 1e-5                                           # truncation ~ h^2 |f'''| / 6, rounding ~ 1e-16 / h: both ~ 1e-10
+    up, _ = SC.lowrank_ref(w.double() + h * D, R, niters, want_grad=False)
+    down, _ = SC.lowrank_ref(w.double() - h * D, R, niters, want_grad=False)
+    slope, want = float(up - down) / (2 * h), float((grad * D).sum())
+    err_d = abs(slope - want) / float(grad.norm())
+    print(f"{name}: fp64 lowrank_ref value against sigma_1^2 {err_v:.2e}; directional derivative {err_d:.2e}")
+    assert err_v <= 1e-9, (name, err_v)
+    assert err_d <= 1e-7, (name, slope, want)
