@@ -132,6 +132,12 @@ __device__ __forceinline__ double bm_wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// The step from a wavefront's value to a workgroup's: lane 0 of every wavefront puts it into sh[wavefront] (the block
+// reductions of bm_block.h are built on it).
+template <typename T>
+__device__ __forceinline__ void bm_wave_to_lds(T v, T* sh) {
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+}
 // max |x| of a tensor, published by the kernel that produces it (consumed as the f16x2 scale of the next
 // contraction, conv_nn_h2w.hip): every workgroup folds its maximum through LDS and stores it to ws[workgroup id]
 // (plain store: no atomics, nothing to zero beforehand); a one-workgroup kernel (bm_amax_finalize, core.hip)
@@ -151,8 +157,7 @@ struct BmAmaxDst {
 __device__ __forceinline__ void bm_publish_amax_at(float m, const BmAmaxDst& dst, float* sh /* >= blockDim / 64 floats of LDS */,
                                                    unsigned wg /* index of the partial: workgroup or tile id */) {
     if (!dst.ws) return;                               // kernel argument: uniform
-    m = bm_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    bm_wave_to_lds(bm_wave_max(m), sh);
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nw = (blockDim.x + 63) >> 6;

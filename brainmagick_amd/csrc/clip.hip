@@ -2,7 +2,7 @@
 // [B, B'] score matrix with the target on the diagonal, probabilities, and the score gradient.
 // The two dense contractions (scores = est . cand^T over K = F*T, and dEst = dScores . cand) run on
 // the MFMA kernels (gemm_nt.hip split-K, conv_nn.hip).
-#include "bm_common.h"
+#include "bm_block.h"
 
 // inv_norm[o] = 1 / (1e-8 + ||cand[o]||_2)      (losses.py:91)
 __global__ __launch_bounds__(256) void inv_norms_kernel(const float* __restrict__ cand, long K,
@@ -129,23 +129,6 @@ extern "C" int bm_flag_unless_all_set(const unsigned char* mask, long n, int* fl
 //   dscaled[b][o]= (probs - [o==b]) / B * inv_norm[o]              (d loss / d(est.cand[o]) )
 // The fold of the split-K partial tiles is the expensive part (nsplit * B * B' * 4 bytes): consecutive threads
 // read consecutive columns of one partial row (coalesced), eight splits in flight per thread.
-__device__ __forceinline__ float clip_block_max(float v, float* sh) {
-    v = bm_wave_max(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    __syncthreads();
-    return v;
-}
-__device__ __forceinline__ float clip_block_sum(float v, float* sh) {
-    v = bm_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return v;
-}
-
 __global__ __launch_bounds__(256) void clip_ce_kernel(const float* __restrict__ part, int nsplit,
                                                       const float* __restrict__ inv_norm, float* __restrict__ scores,
                                                       float* __restrict__ probs, float* __restrict__ dscaled,
@@ -176,10 +159,10 @@ __global__ __launch_bounds__(256) void clip_ce_kernel(const float* __restrict__ 
         srow[o] = s;
         mx = fmaxf(mx, s);
     }
-    mx = clip_block_max(mx, sh);
+    mx = bm_block_max<4>(mx, sh);
     float sum = 0.f;
     for (int o = threadIdx.x; o < Bc; o += 256) sum += expf(srow[o] - mx);      // own writes: same thread, same o
-    sum = clip_block_sum(sum, sh);
+    sum = bm_block_sum<4>(sum, sh);
     const float lse = mx + logf(sum);
     const float inv = 1.f / sum;
     for (int o = threadIdx.x; o < Bc; o += 256) {

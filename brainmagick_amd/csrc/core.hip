@@ -1,5 +1,5 @@
 // Error convention + version of the C-ABI (include/bm_hip.h).
-#include "bm_common.h"
+#include "bm_block.h"
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -30,62 +30,42 @@ extern "C" int bm_device_count(void) {
     return n;
 }
 
-// out[0] = max_i ws[i] (NaN-ignoring fmaxf; partial maxima are >= 0), out[1 .. BM_AMAX_SHARDS) = 0
-__global__ __launch_bounds__(1024) void amax_finalize_kernel(const float* __restrict__ ws, int n, float* __restrict__ out) {
-    __shared__ float sh[16];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += 1024) m = fmaxf(m, ws[i]);
-    m = bm_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x < BM_AMAX_SHARDS) {
-        float v = 0.f;
-        if (threadIdx.x == 0)
-            for (int w = 0; w < 16; ++w) v = fmaxf(v, sh[w]);
-        out[threadIdx.x] = v;
-    }
+// The folds of bm_block.h as launches of their own (one workgroup), for the producers whose workgroups only store.
+#define FIN_THREADS 1024
+#define FIN_WAVES (FIN_THREADS / 64)
+__global__ __launch_bounds__(FIN_THREADS) void amax_finalize_kernel(const float* __restrict__ ws, int n,
+                                                                    float* __restrict__ out) {
+    __shared__ float sh[FIN_WAVES];
+    bm_amax_fold<FIN_WAVES>(ws, n, out, sh);
 }
 
 int bm_amax_finalize(const float* ws, int n, float* out, hipStream_t stream) {
     if (!out) return BM_OK;
-    hipLaunchKernelGGL(amax_finalize_kernel, dim3(1), dim3(1024), 0, stream, ws, n, out);
+    hipLaunchKernelGGL(amax_finalize_kernel, dim3(1), dim3(FIN_THREADS), 0, stream, ws, n, out);
     return bm_check_launch("amax_finalize");
 }
 
 // Partials laid out [nsplit][C] (the (channel, split) grids of the BatchNorm / GLU backward kernels): rows_out[c] =
 // max over the splits -- the per-channel maxima that give every row of a weight gradient its own f16x2 scale
 // (gemm_nt_h2w.hip, RS kernels) -- and the tensor maximum into the slot, in ONE one-workgroup launch.
-__global__ __launch_bounds__(1024) void amax_finalize_rows_kernel(const float* __restrict__ ws, int C, int nsplit,
-                                                                  float* __restrict__ out, float* __restrict__ rows_out,
-                                                                  const double* __restrict__ sum_partial,
-                                                                  float* __restrict__ sums_out) {
-    __shared__ float sh[16];
-    float m = 0.f;
-    for (int c = threadIdx.x; c < C; c += 1024) {
-        float r = 0.f;
-        for (int s = 0; s < nsplit; ++s) r = fmaxf(r, ws[(long)s * C + c]);
-        if (rows_out) rows_out[c] = r;
-        m = fmaxf(m, r);
-        if (sum_partial) {                  // the same launch folds the producer's per-(channel, split) sums (bias gradient)
+__global__ __launch_bounds__(FIN_THREADS) void amax_finalize_rows_kernel(const float* __restrict__ ws, int C, int nsplit,
+                                                                         float* __restrict__ out,
+                                                                         float* __restrict__ rows_out,
+                                                                         const double* __restrict__ sum_partial,
+                                                                         float* __restrict__ sums_out) {
+    __shared__ float sh[FIN_WAVES];
+    if (sum_partial)                        // the same launch folds the producer's per-(channel, split) sums (bias gradient)
+        for (int c = threadIdx.x; c < C; c += FIN_THREADS) {
             double t = 0;
             for (int s = 0; s < nsplit; ++s) t += sum_partial[(long)c * nsplit + s];
             sums_out[c] = (float)t;
         }
-    }
-    m = bm_wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x < BM_AMAX_SHARDS) {
-        float v = 0.f;
-        if (threadIdx.x == 0)
-            for (int w = 0; w < 16; ++w) v = fmaxf(v, sh[w]);
-        out[threadIdx.x] = v;
-    }
+    bm_amax_fold_rows<FIN_WAVES>(ws, C, nsplit, 1, C, out, rows_out, sh);
 }
 
 int bm_amax_finalize_rows(const float* ws, int C, int nsplit, float* out, float* rows_out, hipStream_t stream) {
     if (!out) return BM_OK;
-    hipLaunchKernelGGL(amax_finalize_rows_kernel, dim3(1), dim3(1024), 0, stream, ws, C, nsplit, out, rows_out,
+    hipLaunchKernelGGL(amax_finalize_rows_kernel, dim3(1), dim3(FIN_THREADS), 0, stream, ws, C, nsplit, out, rows_out,
                        (const double*)nullptr, (float*)nullptr);
     return bm_check_launch("amax_finalize_rows");
 }
@@ -93,7 +73,7 @@ int bm_amax_finalize_rows(const float* ws, int C, int nsplit, float* out, float*
 // ... and, in the same launch, sums_out[c] = sum_split sum_partial[c][split] (doubles; the bias gradient of the layer)
 int bm_amax_finalize_rows_sums(const float* ws, int C, int nsplit, float* out, float* rows_out,
                                const double* sum_partial, float* sums_out, hipStream_t stream) {
-    hipLaunchKernelGGL(amax_finalize_rows_kernel, dim3(1), dim3(1024), 0, stream, ws, C, nsplit, out, rows_out,
+    hipLaunchKernelGGL(amax_finalize_rows_kernel, dim3(1), dim3(FIN_THREADS), 0, stream, ws, C, nsplit, out, rows_out,
                        sum_partial, sums_out);
     return bm_check_launch("amax_finalize_rows");
 }

@@ -13,36 +13,28 @@
 // (b, c) in memory order: consecutive lanes store consecutive vectors whatever T is.  A workgroup takes chunks of
 // MI_THREADS * MI_UNROLL consecutive vectors; a thread has MI_UNROLL loads, then MI_UNROLL stores in flight.  No
 // workgroup waits for another: the per-workgroup maxima are folded by the workgroup that finishes last
-// (regress_common.h).  That ticket is one agent-scope atomic per workgroup on one address, about 12 ns each on the
+// (bm_block.h).  That ticket is one agent-scope atomic per workgroup on one address, about 12 ns each on the
 // MI355X -- with 2 048 workgroups of 256 threads it cost more than the stores (40 us against 17 us without the maximum
 // at 256 x 273 x 360); hence few, large workgroups: at most one per CU, 512 threads (19 us).
-#include "regress_common.h"
+#include "bm_block.h"
 
 #define MI_THREADS 512
 #define MI_WAVES (MI_THREADS / 64)
 #define MI_MAX_BLOCKS 256
 #define MI_UNROLL 4
 
-// Workspace (bm_meg_init_workspace_bytes): the ticket counter (zero between launches: the last workgroup resets it),
-// then the per-workgroup partial maxima.
-static const long MI_WS_BYTES = 64 + MI_MAX_BLOCKS * 4L;
+// Workspace (bm_meg_init_workspace_bytes): the ticket counter, then the per-workgroup partial maxima.
+static const long MI_WS_BYTES = BmFoldWs<float>::bytes(MI_MAX_BLOCKS);
 
 extern "C" long bm_meg_init_workspace_bytes(void) { return MI_WS_BYTES; }
-
-__device__ __forceinline__ float mi_block_max(const float* shf) {
-    float m = shf[0];
-#pragma unroll
-    for (int w = 1; w < MI_WAVES; ++w) m = fmaxf(m, shf[w]);
-    return m;
-}
 
 template <int V>
 __global__ __launch_bounds__(MI_THREADS) void meg_init_kernel(const float* __restrict__ meg, float* __restrict__ x,
                                                               unsigned nvec, unsigned Tv, BmFastDiv div_tv, int limit,
                                                               float* __restrict__ amax_out, unsigned* ticket,
                                                               float* part) {
-    typedef typename RgVec<V>::F FV;
-    __shared__ double sh[MI_WAVES / 2 + 1];         // MI_WAVES floats of wavefront maxima, then the last-arriver flag
+    typedef typename BmVec<V>::F FV;
+    __shared__ BmFoldLds<float, MI_WAVES> sh;
     const unsigned chunk = MI_THREADS * MI_UNROLL;
     float mx = 0.f;
     for (unsigned base = blockIdx.x * chunk; base < nvec; base += gridDim.x * chunk) {
@@ -55,12 +47,12 @@ __global__ __launch_bounds__(MI_THREADS) void meg_init_kernel(const float* __res
             const int t = (int)(jc - row * Tv) * V;         // first sample of the vector
             FV v;
 #pragma unroll
-            for (int i = 0; i < V; ++i) rg_set(v, i, 0.f);
+            for (int i = 0; i < V; ++i) bm_set(v, i, 0.f);
             if (t < limit) v = ((const FV*)meg)[jc];
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                const float e = t + i < limit ? rg_get(v, i) : 0.f;
-                rg_set(r[u], i, e);
+                const float e = t + i < limit ? bm_get(v, i) : 0.f;
+                bm_set(r[u], i, e);
                 mx = fmaxf(mx, fabsf(e));
             }
         }
@@ -71,19 +63,8 @@ __global__ __launch_bounds__(MI_THREADS) void meg_init_kernel(const float* __res
         }
     }
     if (!amax_out) return;                              // kernel argument: uniform
-    float* shf = (float*)sh;
-    mx = bm_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) rg_store_partial(part + blockIdx.x, mi_block_max(shf));
-    __syncthreads();
-    if (!rg_last_arriver(ticket, gridDim.x, sh + MI_WAVES / 2)) return;
-    float all = 0.f;
-    for (unsigned k = threadIdx.x; k < gridDim.x; k += MI_THREADS) all = fmaxf(all, part[k]);
-    all = bm_wave_max(all);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = all;
-    __syncthreads();
-    if (threadIdx.x < BM_AMAX_SHARDS) amax_out[threadIdx.x] = threadIdx.x == 0 ? mi_block_max(shf) : 0.f;
+    if (!bm_amax_arrive(mx, part + blockIdx.x, ticket, gridDim.x, sh)) return;
+    bm_amax_fold<MI_WAVES>(part, gridDim.x, amax_out, sh.wave[0]);
 }
 
 extern "C" int bm_meg_init(const float* meg, float* x, int B, int C, int T, int limit, float* amax_out,
@@ -99,14 +80,13 @@ extern "C" int bm_meg_init(const float* meg, float* x, int B, int C, int T, int 
     const unsigned nvec = (unsigned)((long)B * C * T / V), Tv = (unsigned)(T / V);
     int blocks = cdiv(nvec, MI_THREADS * MI_UNROLL);
     blocks = blocks < 1 ? 1 : blocks > MI_MAX_BLOCKS ? MI_MAX_BLOCKS : blocks;
-    unsigned* ticket = amax_out ? (unsigned*)workspace : nullptr;
-    float* part = amax_out ? (float*)((char*)workspace + 64) : nullptr;
+    const BmFoldWs<float> ws = BmFoldWs<float>::at(amax_out ? workspace : nullptr);
     hipStream_t s = (hipStream_t)stream;
     if (vec)
         hipLaunchKernelGGL(meg_init_kernel<4>, dim3(blocks), dim3(MI_THREADS), 0, s, meg, x, nvec, Tv, bm_fastdiv(Tv),
-                           limit, amax_out, ticket, part);
+                           limit, amax_out, ws.tickets, ws.part);
     else
         hipLaunchKernelGGL(meg_init_kernel<1>, dim3(blocks), dim3(MI_THREADS), 0, s, meg, x, nvec, Tv, bm_fastdiv(Tv),
-                           limit, amax_out, ticket, part);
+                           limit, amax_out, ws.tickets, ws.part);
     return bm_check_launch("meg_init");
 }

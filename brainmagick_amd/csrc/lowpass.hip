@@ -18,7 +18,7 @@
 // and row_stride allow it), the pads are copied from the staged first / last sample; no load index leaves
 // [row start, row start + T).  The loads of a workgroup's NEXT rows are issued into registers before the current rows are
 // filtered and land in LDS after them: a workgroup has one CU to itself (64 KB of LDS, at most 256 of them: few, large
-// workgroups and the last-arriver fold of the maxima as in encode.hip), so nothing else hides their latency.
+// workgroups and the last-arriver fold of the maxima, bm_block.h, as in encode.hip): nothing else hides their latency.
 //
 // Measured at 256 x 273 x 360 through the [..., 18:] view, 21 taps (profiles/lowpass_vs_torch.txt; kernel times by
 // rocprofv3): 131 us with 512 threads and no look-ahead, 88-92 us as it is (74 us where x allows 16-byte loads), 1.6 us
@@ -26,7 +26,7 @@
 // filtering are phases of ONE workgroup per CU, separated by barriers, so memory and LDS take turns.  Tried and dropped
 // because the time did not move: storing a round's results one round later (the wait for the loads also waits for the
 // stores in front of it), and staging 12 288 floats at a time.  Two workgroups per CU, or waves that only load, are next.
-#include "regress_common.h"
+#include "bm_block.h"
 
 #define LP_THREADS 1024
 #define LP_WAVES (LP_THREADS / 64)
@@ -34,17 +34,10 @@
 #define LP_LDS 8192                 // floats of staged rows: the largest padded row, T + 2 half
 #define LP_SLACK 16                 // floats the look-ahead reads may run past the staged rows / the taps (never used)
 
-// Workspace (bm_lowpass_workspace_bytes): the ticket counter (zero between launches), then the per-workgroup maxima.
-static const long LP_WS_BYTES = 64 + LP_MAX_BLOCKS * 4L;
+// Workspace (bm_lowpass_workspace_bytes): the ticket counter, then the per-workgroup partial maxima.
+static const long LP_WS_BYTES = BmFoldWs<float>::bytes(LP_MAX_BLOCKS);
 
 extern "C" long bm_lowpass_workspace_bytes(void) { return LP_WS_BYTES; }
-
-__device__ __forceinline__ float lp_block_max(const float* shf) {
-    float m = shf[0];
-#pragma unroll
-    for (int w = 1; w < LP_WAVES; ++w) m = fmaxf(m, shf[w]);
-    return m;
-}
 
 struct LpPlan {
     int R;                  // rows a workgroup stages at a time
@@ -57,9 +50,9 @@ struct LpPlan {
 // The loads of the rows [row0, row0 + nr) into registers: item i = (row, q) is the VL samples from q VL on.  A vector
 // that would cross the end of the row is loaded sample by sample.
 template <int VL>
-__device__ __forceinline__ void lp_load(typename RgVec<VL>::F* pre, const float* __restrict__ x, long row_stride, int row0,
+__device__ __forceinline__ void lp_load(typename BmVec<VL>::F* pre, const float* __restrict__ x, long row_stride, int row0,
                                         int nr, int T, const LpPlan& plan) {
-    typedef typename RgVec<VL>::F FL;
+    typedef typename BmVec<VL>::F FL;
 #pragma unroll
     for (int u = 0; u < LP_LDS / VL / LP_THREADS; ++u) {
         const unsigned i = u * LP_THREADS + threadIdx.x;
@@ -71,7 +64,7 @@ __device__ __forceinline__ void lp_load(typename RgVec<VL>::F* pre, const float*
                 pre[u] = *(const FL*)src;
             } else {
 #pragma unroll
-                for (int e = 0; e < VL; ++e) rg_set(pre[u], e, s + e < T ? src[e] : 0.f);
+                for (int e = 0; e < VL; ++e) bm_set(pre[u], e, s + e < T ? src[e] : 0.f);
             }
         }
     }
@@ -79,7 +72,7 @@ __device__ __forceinline__ void lp_load(typename RgVec<VL>::F* pre, const float*
 
 // ... and from the registers to LDS column half + s of their row.
 template <int VL>
-__device__ __forceinline__ void lp_stage(const typename RgVec<VL>::F* pre, float* smp, int nr, int T, int half,
+__device__ __forceinline__ void lp_stage(const typename BmVec<VL>::F* pre, float* smp, int nr, int T, int half,
                                          const LpPlan& plan) {
 #pragma unroll
     for (int u = 0; u < LP_LDS / VL / LP_THREADS; ++u) {
@@ -90,7 +83,7 @@ __device__ __forceinline__ void lp_stage(const typename RgVec<VL>::F* pre, float
             float* dst = smp + r * plan.Wp + half + s;
 #pragma unroll
             for (int e = 0; e < VL; ++e)
-                if (s + e < T) dst[e] = rg_get(pre[u], e);
+                if (s + e < T) dst[e] = bm_get(pre[u], e);
         }
     }
 }
@@ -101,11 +94,11 @@ __global__ __launch_bounds__(LP_THREADS) void lowpass_kernel(const float* __rest
                                                              const float* __restrict__ taps, int half, LpPlan plan,
                                                              float* __restrict__ amax_out, unsigned* ticket,
                                                              float* part) {
-    typedef typename RgVec<V>::F FV;
-    typedef typename RgVec<VL>::F FL;
+    typedef typename BmVec<V>::F FV;
+    typedef typename BmVec<VL>::F FL;
     __shared__ __attribute__((aligned(16))) float smp[LP_LDS + LP_SLACK];
     __shared__ __attribute__((aligned(16))) float tp[LP_LDS + LP_SLACK];
-    __shared__ double sh[LP_WAVES / 2 + 1];         // LP_WAVES floats of wavefront maxima, then the last-arriver flag
+    __shared__ BmFoldLds<float, LP_WAVES> sh;
     const int ntaps = 2 * half + 1, Wp = plan.Wp, npad = 2 * half;
     const unsigned Tg = (unsigned)(T / V);
     for (int k = threadIdx.x; k < ntaps + 2 * V; k += LP_THREADS) tp[k] = k < ntaps ? taps[k] : 0.f;
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(LP_THREADS) void lowpass_kernel(const float* __rest
             const int t0 = (int)(g - r * Tg) * V;
             FV out;
 #pragma unroll
-            for (int i = 0; i < V; ++i) rg_set(out, i, 0.f);
+            for (int i = 0; i < V; ++i) bm_set(out, i, 0.f);
             if (t0 < keep) {
                 const float* a = smp + r * Wp + t0;
                 FV c0 = *(const FV*)a, c1 = *(const FV*)(a + V), tk = *(const FV*)tp;
@@ -149,13 +142,13 @@ __global__ __launch_bounds__(LP_THREADS) void lowpass_kernel(const float* __rest
                     float w[2 * V];
 #pragma unroll
                     for (int i = 0; i < V; ++i) {
-                        w[i] = rg_get(c0, i);
-                        w[V + i] = rg_get(c1, i);
+                        w[i] = bm_get(c0, i);
+                        w[V + i] = bm_get(c1, i);
                     }
 #pragma unroll
                     for (int j = 0; j < V; ++j) {
                         if (kb + j < ntaps) {                       // uniform
-                            const float c = rg_get(tk, j);
+                            const float c = bm_get(tk, j);
 #pragma unroll
                             for (int i = 0; i < V; ++i) acc[i] = fmaf(c, w[i + j], acc[i]);
                         }
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(LP_THREADS) void lowpass_kernel(const float* __rest
 #pragma unroll
                 for (int i = 0; i < V; ++i) {
                     const float e = t0 + i < keep ? acc[i] : 0.f;
-                    rg_set(out, i, e);
+                    bm_set(out, i, e);
                     mx = fmaxf(mx, fabsf(e));
                 }
             }
@@ -177,19 +170,8 @@ __global__ __launch_bounds__(LP_THREADS) void lowpass_kernel(const float* __rest
         row0 = next;
     }
     if (!amax_out) return;                              // kernel argument: uniform
-    float* shf = (float*)sh;
-    mx = bm_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) rg_store_partial(part + blockIdx.x, lp_block_max(shf));
-    __syncthreads();
-    if (!rg_last_arriver(ticket, gridDim.x, sh + LP_WAVES / 2)) return;
-    float all = 0.f;
-    for (unsigned k = threadIdx.x; k < gridDim.x; k += LP_THREADS) all = fmaxf(all, part[k]);
-    all = bm_wave_max(all);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = all;
-    __syncthreads();
-    if (threadIdx.x < BM_AMAX_SHARDS) amax_out[threadIdx.x] = threadIdx.x == 0 ? lp_block_max(shf) : 0.f;
+    if (!bm_amax_arrive(mx, part + blockIdx.x, ticket, gridDim.x, sh)) return;
+    bm_amax_fold<LP_WAVES>(part, gridDim.x, amax_out, sh.wave[0]);
 }
 
 extern "C" int bm_lowpass(const float* x, long row_stride, float* y, int rows, int T, int keep, const float* taps,
@@ -218,12 +200,11 @@ extern "C" int bm_lowpass(const float* x, long row_stride, float* y, int rows, i
     plan.div_nq = bm_fastdiv(plan.nq > 0 ? plan.nq : 1);
     plan.div_pad = bm_fastdiv(half > 0 ? 2 * half : 1);
     plan.div_tg = bm_fastdiv(vec ? T / 4 : T);
-    unsigned* ticket = amax_out ? (unsigned*)workspace : nullptr;
-    float* part = amax_out ? (float*)((char*)workspace + 64) : nullptr;
+    const BmFoldWs<float> ws = BmFoldWs<float>::at(amax_out ? workspace : nullptr);
     hipStream_t s = (hipStream_t)stream;
 #define LP_LAUNCH(V, VL)                                                                                        \
     hipLaunchKernelGGL((lowpass_kernel<V, VL>), dim3(blocks), dim3(LP_THREADS), 0, s, x, row_stride, y, rows, T, keep, \
-                       taps, half, plan, amax_out, ticket, part)
+                       taps, half, plan, amax_out, ws.tickets, ws.part)
     if (vec && vload)
         LP_LAUNCH(4, 4);
     else if (vec)

@@ -8,10 +8,10 @@
 //
 // The mask is null (all true), [B][1][T] (broadcast over F: SegmentBatch.features_mask) or [B][F][T]; one byte per
 // element, nonzero = selected.  The forward and the backward are ONE launch each: the loss' per-workgroup fp64
-// partials, and the backward's per-(channel, split) maxima, are folded by the workgroup that finishes last (ticket
-// counter in the caller's workspace; partials stored write-through, an agent-scope acquire in the last workgroup).  Every sum has a fixed order for a given shape: the results are bit-reproducible.
-#include "bm_common.h"
-#include "regress_common.h"
+// partials, and the backward's per-(channel, split) maxima, are folded by the workgroup that finishes last (bm_block.h:
+// ticket counter in the caller's workspace; partials stored write-through, an agent-scope acquire in the last
+// workgroup).  Every sum has a fixed order for a given shape: the results are bit-reproducible.
+#include "bm_block.h"
 
 #define RG_THREADS 256
 #define RG_FWD_MAX_BLOCKS 1024
@@ -37,29 +37,22 @@ struct RgWs {
     double* part_fd;        // [FD_SLOTS][2][FD_MAX_BLOCKS]
 };
 static RgWs rg_ws(void* base) {
-    char* p = (char*)base;
+    const BmFoldWs<double> head = BmFoldWs<double>::at(base);
     RgWs w;
-    w.tickets = (unsigned*)p;
-    w.part_sum = (double*)(p + 64);
+    w.tickets = head.tickets;
+    w.part_sum = head.part;
     w.part_cnt = w.part_sum + RG_FWD_MAX_BLOCKS;
     w.part_max = (float*)(w.part_cnt + RG_FWD_MAX_BLOCKS);
     w.part_fd = (double*)(w.part_max + RG_BWD_MAX_PARTIALS);
     return w;
 }
-static const long RG_WS_BYTES = 64 + 2L * RG_FWD_MAX_BLOCKS * 8 + RG_BWD_MAX_PARTIALS * 4L +
+static const long RG_WS_BYTES = BmFoldWs<double>::bytes(2L * RG_FWD_MAX_BLOCKS) + RG_BWD_MAX_PARTIALS * 4L +
                                 2L * FD_SLOTS * FD_MAX_BLOCKS * 8;
 
 extern "C" long bm_regress_workspace_bytes(void) { return RG_WS_BYTES; }
 
-// fixed-order block sum of a double (4 wavefronts); sh: >= 4 doubles; returns the sum in every thread
-__device__ __forceinline__ double rg_block_sum(double v, double* sh) {
-    v = bm_wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return v;
-}
+#define RG_WAVES (RG_THREADS / 64)
+typedef BmFoldLds<double, RG_WAVES, 2> RgSumLds;          // two sums at a time: (numerator, denominator)
 
 // ---- forward: one launch, grid-stride over vectors of V elements (V = 4 when T % 4 == 0) ----------------------------
 template <int V>
@@ -70,9 +63,9 @@ __global__ __launch_bounds__(RG_THREADS) void regress_fwd_kernel(const float* __
                                                                  BmFastDiv div_f, int kind, RgWs ws,
                                                                  float* __restrict__ loss, double* __restrict__ count,
                                                                  int* __restrict__ flag) {
-    typedef typename RgVec<V>::F FV;
-    typedef typename RgVec<V>::M MV;
-    __shared__ double sh[9];
+    typedef typename BmVec<V>::F FV;
+    typedef typename BmVec<V>::M MV;
+    __shared__ RgSumLds sh;
     double s = 0.0, c = 0.0;
     for (unsigned j = blockIdx.x * RG_THREADS + threadIdx.x; j < nvec; j += gridDim.x * RG_THREADS) {
         const FV e = ((const FV*)est)[j];
@@ -87,20 +80,20 @@ __global__ __launch_bounds__(RG_THREADS) void regress_fwd_kernel(const float* __
         }
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const bool sel = mask_mode == RG_MASK_NONE || rg_get(m, i) != 0;
-            const double d = (double)(rg_get(e, i) - rg_get(o, i));      // the fp32 difference, as torch forms it
+            const bool sel = mask_mode == RG_MASK_NONE || bm_get(m, i) != 0;
+            const double d = (double)(bm_get(e, i) - bm_get(o, i));      // the fp32 difference, as torch forms it
             const double w = kind == RG_L1 ? fabs(d) : d * d;
             s += sel ? w : 0.0;
             c += sel ? 1.0 : 0.0;
         }
     }
-    s = rg_block_sum(s, sh);
-    c = rg_block_sum(c, sh + 4);
+    s = bm_block_sum<RG_WAVES>(s, sh.wave[0]);
+    c = bm_block_sum<RG_WAVES>(c, sh.wave[1]);
     if (threadIdx.x == 0) {
-        rg_store_partial(ws.part_sum + blockIdx.x, s);
-        rg_store_partial(ws.part_cnt + blockIdx.x, c);
+        bm_store_partial(ws.part_sum + blockIdx.x, s);
+        bm_store_partial(ws.part_cnt + blockIdx.x, c);
     }
-    if (!rg_last_arriver(ws.tickets + 0, gridDim.x, sh + 8)) return;
+    if (!bm_last_arriver(ws.tickets + 0, gridDim.x, &sh.last)) return;
     // the last workgroup folds the partials in block order
     s = 0.0;
     c = 0.0;
@@ -108,8 +101,8 @@ __global__ __launch_bounds__(RG_THREADS) void regress_fwd_kernel(const float* __
         s += ws.part_sum[k];
         c += ws.part_cnt[k];
     }
-    s = rg_block_sum(s, sh);
-    c = rg_block_sum(c, sh + 4);
+    s = bm_block_sum<RG_WAVES>(s, sh.wave[0]);
+    c = bm_block_sum<RG_WAVES>(c, sh.wave[1]);
     if (threadIdx.x == 0) {
         *loss = (float)(s / c);                       // count == 0: 0 / 0 = NaN, like torch's mean of nothing
         *count = c;
@@ -157,9 +150,9 @@ __global__ __launch_bounds__(RG_THREADS) void regress_bwd_kernel(const float* __
                                                                  float* __restrict__ d_est, float* __restrict__ d_out,
                                                                  float* __restrict__ amax_out,
                                                                  float* __restrict__ amax_rows_out, RgWs ws) {
-    typedef typename RgVec<V>::F FV;
-    typedef typename RgVec<V>::M MV;
-    __shared__ double sh[9];
+    typedef typename BmVec<V>::F FV;
+    typedef typename BmVec<V>::M MV;
+    __shared__ BmFoldLds<float, RG_WAVES> sh;
     const int split = blockIdx.x, f = blockIdx.y, nsplit = gridDim.x;
     const int b0 = split * bper;
     const int nb = min(B, b0 + bper) - b0;
@@ -183,38 +176,21 @@ __global__ __launch_bounds__(RG_THREADS) void regress_bwd_kernel(const float* __
         FV r;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const bool sel = mask_mode == RG_MASK_NONE || rg_get(m, i) != 0;
-            const float d = rg_get(e, i) - rg_get(o, i);
+            const bool sel = mask_mode == RG_MASK_NONE || bm_get(m, i) != 0;
+            const float d = bm_get(e, i) - bm_get(o, i);
             float v;
             if (kind == RG_L1) v = d > 0.f ? scale : d < 0.f ? -scale : 0.f;   // torch's sign: (0 < d) - (d < 0), 0 for 0 AND for NaN
             else v = d * scale * g;
             v = sel ? v : 0.f;
-            rg_set(r, i, v);
+            bm_set(r, i, v);
             mx = fmaxf(mx, fabsf(v));
         }
         ((FV*)d_est)[idx] = r;
         if (d_out) ((FV*)d_out)[idx] = -r;
     }
     if (!amax_out) return;                            // kernel argument: uniform
-    float* shf = (float*)sh;
-    mx = bm_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) rg_store_partial(ws.part_max + f * nsplit + split, fmaxf(fmaxf(shf[0], shf[1]), fmaxf(shf[2], shf[3])));
-    __syncthreads();
-    if (!rg_last_arriver(ws.tickets + 1, gridDim.x * gridDim.y, sh + 8)) return;
-    float all = 0.f;
-    for (int c = threadIdx.x; c < F; c += RG_THREADS) {
-        float v = 0.f;
-        for (int k = 0; k < nsplit; ++k) v = fmaxf(v, ws.part_max[c * nsplit + k]);
-        if (amax_rows_out) amax_rows_out[c] = v;
-        all = fmaxf(all, v);
-    }
-    all = bm_wave_max(all);
-    if ((threadIdx.x & 63) == 0) shf[threadIdx.x >> 6] = all;
-    __syncthreads();
-    if (threadIdx.x < BM_AMAX_SHARDS)
-        amax_out[threadIdx.x] = threadIdx.x == 0 ? fmaxf(fmaxf(shf[0], shf[1]), fmaxf(shf[2], shf[3])) : 0.f;
+    if (!bm_amax_arrive(mx, ws.part_max + f * nsplit + split, ws.tickets + 1, gridDim.x * gridDim.y, sh)) return;
+    bm_amax_fold_rows<RG_WAVES>(ws.part_max, F, nsplit, nsplit, 1, amax_out, amax_rows_out, sh.wave[0]);
 }
 
 extern "C" int bm_regress_loss_bwd(const float* est, const float* out, const unsigned char* mask, int mask_mode,
@@ -370,17 +346,18 @@ __global__ __launch_bounds__(RG_THREADS) void feature_decoding_fwd_kernel(
     const float* __restrict__ weights, FdTable tab, unsigned npos, unsigned ntiles, int C, int Co, unsigned T,
     BmFastDiv div_t, RgWs ws, float* __restrict__ loss, float* __restrict__ terms, double* __restrict__ denoms,
     float* __restrict__ lse, int* __restrict__ flag) {
-    __shared__ double sh[9 + 2 * RG_THREADS];
-    double* sh_s = sh + 9;
-    double* sh_m = sh_s + RG_THREADS;
+    __shared__ struct {
+        RgSumLds sums;
+        double s[RG_THREADS], m[RG_THREADS];      // a categorical feature's running (sum, maximum) of every thread
+    } sh;
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int bad = 0;
     double cnt = 0.0;
     if (wave == 0)
         for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
             cnt += fd_pos(tile, npos, T, div_t, mask).sel ? 1.0 : 0.0;
-    cnt = rg_block_sum(cnt, sh);
-    if (threadIdx.x == 0) rg_store_partial(fd_part(ws, FD_MAX_FEATURES, 0) + blockIdx.x, cnt);
+    cnt = bm_block_sum<RG_WAVES>(cnt, sh.sums.wave[0]);
+    if (threadIdx.x == 0) bm_store_partial(fd_part(ws, FD_MAX_FEATURES, 0) + blockIdx.x, cnt);
     int ci = 0;
     for (int f = 0; f < tab.n; ++f) {
         const FdFeature ft = tab.f[f];
@@ -428,19 +405,19 @@ __global__ __launch_bounds__(RG_THREADS) void feature_decoding_fwd_kernel(
                     for (int i = 0; i < FD_UNROLL; ++i) s += k0 + 4 * i < K ? (double)expf(xv[i] - base) : 0.0;
                     m = cm;
                 }
-                sh_m[threadIdx.x] = (double)m;
-                sh_s[threadIdx.x] = s;
+                sh.m[threadIdx.x] = (double)m;
+                sh.s[threadIdx.x] = s;
                 __syncthreads();
                 if (wave == 0) {
                     float mw[4];
 #pragma unroll
-                    for (int w = 0; w < 4; ++w) mw[w] = (float)sh_m[w * 64 + lane];
+                    for (int w = 0; w < 4; ++w) mw[w] = (float)sh.m[w * 64 + lane];
                     const float mx = fmaxf(fmaxf(mw[0], mw[1]), fmaxf(mw[2], mw[3]));
                     const float base = mx == -INFINITY ? 0.f : mx;
                     double S = 0.0;
 #pragma unroll
                     for (int w = 0; w < 4; ++w)
-                        S += sh_s[w * 64 + lane] * (mw[w] == -INFINITY ? 1.0 : (double)expf(mw[w] - base));
+                        S += sh.s[w * 64 + lane] * (mw[w] == -INFINITY ? 1.0 : (double)expf(mw[w] - base));
                     const double l = (double)base + log(S);
                     const float tv = out[((size_t)p.b * Co + ft.out_start) * T + p.t];
                     int y;
@@ -457,20 +434,20 @@ __global__ __launch_bounds__(RG_THREADS) void feature_decoding_fwd_kernel(
             }
             ++ci;
         }
-        num = rg_block_sum(num, sh);
-        den = rg_block_sum(den, sh + 4);
+        num = bm_block_sum<RG_WAVES>(num, sh.sums.wave[0]);
+        den = bm_block_sum<RG_WAVES>(den, sh.sums.wave[1]);
         if (threadIdx.x == 0) {
-            rg_store_partial(fd_part(ws, f, 0) + blockIdx.x, num);
-            rg_store_partial(fd_part(ws, f, 1) + blockIdx.x, den);
+            bm_store_partial(fd_part(ws, f, 0) + blockIdx.x, num);
+            bm_store_partial(fd_part(ws, f, 1) + blockIdx.x, den);
         }
     }
     const int any_bad = __syncthreads_or(bad);
     if (any_bad && flag && threadIdx.x == 0) atomicOr(flag, FD_RANGE_BIT);
-    if (!rg_last_arriver(ws.tickets + 2, gridDim.x, sh + 8)) return;
+    if (!bm_last_arriver(ws.tickets + 2, gridDim.x, &sh.sums.last)) return;
     // the last workgroup folds the partials in block order, feature by feature
     double nsel = 0.0;
     for (unsigned k = threadIdx.x; k < gridDim.x; k += RG_THREADS) nsel += fd_part(ws, FD_MAX_FEATURES, 0)[k];
-    nsel = rg_block_sum(nsel, sh);
+    nsel = bm_block_sum<RG_WAVES>(nsel, sh.sums.wave[0]);
     float total = 0.f;
     for (int f = 0; f < tab.n; ++f) {
         double num = 0.0, den = 0.0;
@@ -478,8 +455,8 @@ __global__ __launch_bounds__(RG_THREADS) void feature_decoding_fwd_kernel(
             num += fd_part(ws, f, 0)[k];
             den += fd_part(ws, f, 1)[k];
         }
-        num = rg_block_sum(num, sh);
-        den = rg_block_sum(den, sh + 4);
+        num = bm_block_sum<RG_WAVES>(num, sh.sums.wave[0]);
+        den = bm_block_sum<RG_WAVES>(den, sh.sums.wave[1]);
         if (tab.f[f].kind == FD_CONTINUOUS) den = nsel * (double)tab.f[f].width;
         if (threadIdx.x == 0) {
             const float term = (float)(num / den);    // nothing selected: 0 / 0 = NaN, like torch's mean of nothing

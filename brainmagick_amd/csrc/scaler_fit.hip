@@ -9,7 +9,7 @@
 // only (LDS histograms, integer global adds): order-independent, two runs are bit-identical.  A column is split over
 // several workgroups; they never wait for each other inside a launch -- every digit is one counting launch and one
 // small per-channel scan launch, ordered by the stream.
-#include "bm_common.h"
+#include "bm_block.h"
 
 #define SF_THREADS 256
 #define SF_MAXQ 8
@@ -73,16 +73,6 @@ __device__ __forceinline__ void sf_load_mask(const unsigned char* __restrict__ p
     } else {
         m[0] = *p;
     }
-}
-
-// fixed-order block sum of a double (4 wavefronts); sh: >= 4 doubles; returns the sum in every thread
-__device__ __forceinline__ double sf_block_sum(double v, double* sh) {
-    v = bm_wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return v;
 }
 
 // ---- (a) quantile select -------------------------------------------------------------------------------------------
@@ -305,8 +295,8 @@ __global__ __launch_bounds__(SF_THREADS) void sf_moments_kernel(const float* __r
             cnt += m[i] ? 1.0 : 0.0;
         }
     }
-    s = sf_block_sum(s, sh);
-    cnt = sf_block_sum(cnt, sh + 4);
+    s = bm_block_sum<SF_THREADS / 64>(s, sh);
+    cnt = bm_block_sum<SF_THREADS / 64>(cnt, sh + 4);
     if (threadIdx.x == 0) {
         part_sum[ch * nsplit + split] = s;
         part_cnt[ch * nsplit + split] = cnt;
@@ -326,8 +316,8 @@ __global__ __launch_bounds__(SF_THREADS) void sf_moments_fold_kernel(const doubl
             gs += part_sum[k];
             gc += part_cnt[k];
         }
-        gs = sf_block_sum(gs, sh);
-        gc = sf_block_sum(gc, sh + 4);
+        gs = bm_block_sum<SF_THREADS / 64>(gs, sh);
+        gc = bm_block_sum<SF_THREADS / 64>(gc, sh + 4);
     }
     for (int ch = threadIdx.x; ch < nch; ch += SF_THREADS) {
         double s = gs, c = gc;

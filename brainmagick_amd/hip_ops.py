@@ -107,19 +107,42 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _req(t: torch.Tensor, name: str, dtype=torch.float32):
+def _req(t: torch.Tensor, name: str, dtype=torch.float32, contiguous: bool = True):
+    """``contiguous=False``: the caller reads a strided view in place, or makes its own copy."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise BmHipError(f"{name}: expected a GPU tensor; the brainmagick_amd hot path has no CPU "
                          "fallback (got %s)" % (t.device if isinstance(t, torch.Tensor) else type(t)))
     if t.dtype != dtype:
         raise BmHipError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise BmHipError(f"{name}: expected a contiguous tensor")
     return t
 
 
 def _opt(t, name, dtype=torch.float32):
     return None if t is None else _req(t, name, dtype)
+
+
+# Scratch that the kernels of one stream share (they run in order): one buffer per (kind, device, stream).
+# kind -> (size function of the library, dtype, zeroed).  A ZEROED buffer holds ticket counters next to its partials
+# (csrc/bm_block.h): every launch leaves its counter at zero again.
+_WS_KINDS = {
+    "amax": ("bm_amax_ws_elems", torch.float32, False),                 # per-workgroup partial maxima of the producers
+    "regress": ("bm_regress_workspace_bytes", torch.uint8, True),      # csrc/regress.hip
+    "encode": ("bm_meg_init_workspace_bytes", torch.uint8, True),      # csrc/encode.hip
+    "lowpass": ("bm_lowpass_workspace_bytes", torch.uint8, True),      # csrc/lowpass.hip
+}
+_stream_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
+
+
+def _stream_ws(kind: str, device) -> torch.Tensor:
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _stream_workspaces.get(key)
+    if ws is None:
+        size, dtype, zeroed = _WS_KINDS[kind]
+        alloc = torch.zeros if zeroed else torch.empty
+        ws = _stream_workspaces[key] = alloc(getattr(lib(), size)(), device=device, dtype=dtype)
+    return ws
 
 
 # ------------------------------------------------------------------------------------------------
@@ -165,24 +188,13 @@ def amax(x: torch.Tensor, nonfinite_flag: tp.Optional[torch.Tensor] = None) -> t
     global amax_scans
     amax_scans += 1
     out = torch.empty(AMAX_SHARDS, device=x.device, dtype=torch.float32)
-    check(lib().bm_amax_checked(_p(x), x.numel(), _p(out), _p(_amax_ws(x.device)),
+    check(lib().bm_amax_checked(_p(x), x.numel(), _p(out), _p(_stream_ws("amax", x.device)),
                                 _p(_opt(nonfinite_flag, "nonfinite_flag", torch.int32)), _stream()), "bm_amax")
     _note(x, "_bm_amax", out, nonfinite_flag is not None)
     return out
 
 
 _amax_pool: tp.Dict[torch.device, tp.List[tp.Any]] = {}
-_amax_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
-
-
-def _amax_ws(device) -> torch.Tensor:
-    """Scratch for the per-workgroup partial maxima: one buffer per (device, stream); kernels of one stream run in
-    order, so every producer of that stream can use the same buffer."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _amax_workspaces.get(key)
-    if ws is None:
-        ws = _amax_workspaces[key] = torch.empty(lib().bm_amax_ws_elems(), device=device, dtype=torch.float32)
-    return ws
 
 
 def _amax_slot(t: torch.Tensor) -> tp.Optional[torch.Tensor]:
@@ -219,7 +231,7 @@ def row_amax_of(t: torch.Tensor) -> tp.Optional[torch.Tensor]:
 
 def _slot_args(slot):
     """(amax_out, amax_ws) arguments of a producer."""
-    return (_p(slot), _p(_amax_ws(slot.device)) if slot is not None else None)
+    return (_p(slot), _p(_stream_ws("amax", slot.device)) if slot is not None else None)
 
 
 def _touched(t: torch.Tensor) -> torch.Tensor:
@@ -931,18 +943,6 @@ def flag_unless_all_set(mask: torch.Tensor, flag: torch.Tensor) -> None:
 REGRESS_KINDS = {"l1": 0, "mse": 1}
 METRIC_PLANES = 8          # sum l r m, sum l m, sum r m, sum (l m)^2, sum (r m)^2, sum m, sum ((l-r) m)^2, sum |(l-r) m|
 NO_MASK_BIT = 2            # flag word slot 2: "no mask!" (bm/solver.py:354-356); bit 1 there is ClipLoss' mask assert
-_regress_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
-
-
-def _regress_ws(device) -> torch.Tensor:
-    """Partials + ticket counters of the regression kernels: one ZEROED buffer per (device, stream); every launch
-    leaves its counter at zero again."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _regress_workspaces.get(key)
-    if ws is None:
-        ws = _regress_workspaces[key] = torch.zeros(lib().bm_regress_workspace_bytes(), device=device,
-                                                    dtype=torch.uint8)
-    return ws
 
 
 def _regress_mask(mask: tp.Optional[torch.Tensor], shape, what: str):
@@ -970,7 +970,7 @@ def regress_loss_fwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[tor
     B, F, T = est.shape
     loss = torch.empty((), device=est.device, dtype=torch.float32)
     count = torch.empty((), device=est.device, dtype=torch.float64)
-    ws = _regress_ws(est.device)
+    ws = _stream_ws("regress", est.device)
     check(lib().bm_regress_loss_fwd(_p(est), _p(out), _p(mask), mode, B, F, T, REGRESS_KINDS[kind], _p(loss),
                                     _p(count), _p(ws), ws.numel(), _p(_opt(flag, "flag", torch.int32)), _stream()),
           "bm_regress_loss_fwd")
@@ -988,7 +988,7 @@ def regress_loss_bwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional[tor
     dest = torch.empty_like(est)
     dout = torch.empty_like(out) if want_dout else None
     slot = _amax_slot(dest)
-    ws = _regress_ws(est.device)
+    ws = _stream_ws("regress", est.device)
     check(lib().bm_regress_loss_bwd(_p(est), _p(out), _p(mask), mode, B, F, T, REGRESS_KINDS[kind],
                                     _p(_req(grad_out, "grad_out")), _p(_req(count, "count", torch.float64)),
                                     _p(dest), _p(dout), _p(slot), _p(_row_amax_out(dest, slot)), _p(ws), ws.numel(),
@@ -1000,11 +1000,8 @@ def regress_metric_update(est: torch.Tensor, out: torch.Tensor, mask: tp.Optiona
                           t0: int = 0) -> torch.Tensor:
     """acc [METRIC_PLANES, F, T - t0] fp64 += the per-(f, t) sums over the batch of est / out [B, F, T] (fp32; a channel
     slice of a contiguous tensor is read in place), columns t >= t0 only.  mask: bool [B, 1, T] or [B, F, T], or None."""
-    for t, n in ((est, "est"), (out, "out")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            _req(t, f"regress_metric_update.{n}")
-        if t.dtype != torch.float32:
-            raise BmHipError(f"regress_metric_update.{n}: expected dtype torch.float32, got {t.dtype}")
+    _req(est, "regress_metric_update.est", contiguous=False)
+    _req(out, "regress_metric_update.out", contiguous=False)
     if est.dim() != 3 or out.shape != est.shape:
         raise BmHipError(f"regress_metric_update: est {tuple(est.shape)} / out {tuple(out.shape)}: same [B, F, T]")
     B, F, T = est.shape
@@ -1025,20 +1022,6 @@ def regress_metric_update(est: torch.Tensor, out: torch.Tensor, mask: tp.Optiona
 
 
 # The encode task's model input (csrc/encode.hip).
-_encode_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
-
-
-def _encode_ws(device) -> torch.Tensor:
-    """Ticket counter + partial maxima of ``bm_meg_init``: one ZEROED buffer per (device, stream); every launch leaves
-    its counter at zero again."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _encode_workspaces.get(key)
-    if ws is None:
-        ws = _encode_workspaces[key] = torch.zeros(lib().bm_meg_init_workspace_bytes(), device=device,
-                                                   dtype=torch.uint8)
-    return ws
-
-
 def meg_init(meg: torch.Tensor, limit: int) -> torch.Tensor:
     """x = meg for the samples t < limit, 0 for the others (bm/solver.py:288-292, ``mask * meg``): contiguous fp32
     [B, C, T] in, a new tensor out -- one launch that reads only the head and, in f16x2 mode, publishes max |x| (the
@@ -1049,7 +1032,7 @@ def meg_init(meg: torch.Tensor, limit: int) -> torch.Tensor:
     B, C, T = meg.shape
     x = torch.empty_like(meg)
     slot = _amax_slot(x)
-    ws = _encode_ws(meg.device) if slot is not None else None
+    ws = _stream_ws("encode", meg.device) if slot is not None else None
     check(lib().bm_meg_init(_p(meg), _p(x), B, C, T, max(0, min(int(limit), T)), _p(slot), _p(ws), ws.numel() if ws is not None else 0,
                             _stream()), "bm_meg_init")
     return x
@@ -1057,7 +1040,6 @@ def meg_init(meg: torch.Tensor, limit: int) -> torch.Tensor:
 
 # task.lowpass (csrc/lowpass.hip): julius.lowpass_filter with stride 1 and pad=True.
 _lowpass_taps: tp.Dict[tp.Any, tp.Tuple[torch.Tensor, int]] = {}
-_lowpass_workspaces: tp.Dict[tp.Any, torch.Tensor] = {}
 
 
 def _check_cutoff(cutoff: float) -> None:
@@ -1098,16 +1080,6 @@ def lowpass_taps(cutoff: float, zeros: float = 8, device=None) -> tp.Tuple[torch
     return taps, half
 
 
-def _lowpass_ws(device) -> torch.Tensor:
-    """Ticket counter + partial maxima of ``bm_lowpass``: one ZEROED buffer per (device, stream), as ``_encode_ws``."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _lowpass_workspaces.get(key)
-    if ws is None:
-        ws = _lowpass_workspaces[key] = torch.zeros(lib().bm_lowpass_workspace_bytes(), device=device,
-                                                    dtype=torch.uint8)
-    return ws
-
-
 def _uniform_rows(x: torch.Tensor) -> tp.Optional[int]:
     """The distance in elements between consecutive rows of ``x`` seen as [rows, T] -- unit stride in the last
     dimension, every leading dimension a whole number of the one behind it -- or None when ``x`` has no such form."""
@@ -1142,11 +1114,7 @@ def lowpass_filter(x: torch.Tensor, cutoff: float, stride: int = 1, pad: bool = 
     if not pad:
         raise NotImplementedError("lowpass_filter: pad=False (julius' valid convolution) is not built")
     _check_cutoff(cutoff)
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise BmHipError("lowpass_filter.x: expected a GPU tensor; the brainmagick_amd hot path has no CPU fallback "
-                         "(got %s)" % (x.device if isinstance(x, torch.Tensor) else type(x)))
-    if x.dtype != torch.float32:
-        raise BmHipError(f"lowpass_filter.x: expected dtype torch.float32, got {x.dtype}")
+    _req(x, "lowpass_filter.x", contiguous=False)
     if x.dim() < 1 or x.shape[-1] < 1:
         raise BmHipError(f"lowpass_filter: x {tuple(x.shape)} has no samples in its last dimension")
     taps, half = lowpass_taps(cutoff, zeros, x.device)
@@ -1159,7 +1127,7 @@ def lowpass_filter(x: torch.Tensor, cutoff: float, stride: int = 1, pad: bool = 
     if row_stride is None:
         x, row_stride = x.contiguous(), T
     slot = _amax_slot(y) if publish_amax else None
-    ws = _lowpass_ws(x.device) if slot is not None else None
+    ws = _stream_ws("lowpass", x.device) if slot is not None else None
     check(lib().bm_lowpass(_p(x), row_stride, _p(y), rows, T, T if keep is None else max(0, min(int(keep), T)),
                            _p(taps), half, _p(slot), _p(ws), ws.numel() if ws is not None else 0, _stream()),
           "bm_lowpass")
@@ -1206,7 +1174,7 @@ def feature_decoding_fwd(est: torch.Tensor, out: torch.Tensor, mask: tp.Optional
     terms = torch.empty(n, device=est.device, dtype=torch.float32)
     denoms = torch.empty(n, device=est.device, dtype=torch.float64)
     lse = torch.empty(n_cat, B, T, device=est.device, dtype=torch.float32)
-    ws = _regress_ws(est.device)
+    ws = _stream_ws("regress", est.device)
     check(lib().bm_feature_decoding_fwd(_p(est), _p(out), _p(mask), _p(weights),
                                         0 if weights is None else weights.numel(), rows, n, B, C, Co, T, _p(loss),
                                         _p(terms), _p(denoms), _p(lse), _p(ws), ws.numel(),
@@ -1234,11 +1202,8 @@ def class_acc_update(est: torch.Tensor, target: torch.Tensor, mask: tp.Optional[
     """acc [2, T - t0] int64 (hits, selected count) += over the batch of est [B, K, T] (logits) against target [B, 1, T]
     (the class as a float), columns t >= t0 only; channel slices of contiguous tensors are read in place.  mask: bool
     [B, 1, T] or None."""
-    for t, n in ((est, "est"), (target, "target")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            _req(t, f"class_acc_update.{n}")
-        if t.dtype != torch.float32:
-            raise BmHipError(f"class_acc_update.{n}: expected dtype torch.float32, got {t.dtype}")
+    _req(est, "class_acc_update.est", contiguous=False)
+    _req(target, "class_acc_update.target", contiguous=False)
     if est.dim() != 3 or target.dim() != 3 or tuple(target.shape) != (est.shape[0], 1, est.shape[2]):
         raise BmHipError(f"class_acc_update: est {tuple(est.shape)} / target {tuple(target.shape)}: [B, K, T] and "
                          "[B, 1, T]")

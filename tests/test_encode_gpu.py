@@ -153,8 +153,8 @@ def test_meg_init_stays_inside_its_buffers(H, B, C, T, limit):
     (tests/test_guard_bands_gpu.py's arena)."""
     from test_guard_bands_gpu import Arena, _no_nan
     H.set_compute_dtype("f16x2")
-    saved = dict(H._encode_workspaces), dict(H._amax_pool)
-    H._encode_workspaces.clear()
+    saved = dict(H._stream_workspaces), dict(H._amax_pool)
+    H._stream_workspaces.clear()
     H._amax_pool.clear()
     try:
         meg = torch.randn(B, C, T, generator=_gen(T)).cuda()
@@ -167,9 +167,9 @@ def test_meg_init_stays_inside_its_buffers(H, B, C, T, limit):
         assert bool((x == _reference(meg, limit)).all())
         assert float(slot.max()) == float(meg[..., :limit].abs().max())
     finally:
-        H._encode_workspaces.clear()
+        H._stream_workspaces.clear()
         H._amax_pool.clear()
-        H._encode_workspaces.update(saved[0])
+        H._stream_workspaces.update(saved[0])
         H._amax_pool.update(saved[1])
         H.set_compute_dtype(H.DEFAULT_COMPUTE_DTYPE)
 
