@@ -20,7 +20,7 @@ int bm_check_launch(const char* what) {
 }
 
 extern "C" const char* bm_last_error(void) { return bm_err_buf; }
-extern "C" int bm_version(void) { return 111; }   // 0.1.11: optim.svd (bm_spectral_*)
+extern "C" int bm_version(void) { return 112; }   // 0.1.12: the segment loader (bm_segment_*)
 
 // Number of HIP devices visible; <0 on error.  Lets the Python side fail loudly early.
 extern "C" int bm_device_count(void) {

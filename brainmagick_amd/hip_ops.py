@@ -1582,3 +1582,62 @@ def spectral_bwd(plan: SpectralPlan, gscale: torch.Tensor) -> tp.List[torch.Tens
               "bm_spectral_bwd")
     _timed("spectral_bwd", 0., launch)
     return [flat[off:off + torch.Size(shape).numel()].view(shape) for off, shape in zip(plan.grad_offsets, plan.shapes)]
+
+
+# ------------------------------------------------------------------------------------------------
+# The data loader's batch (csrc/segments.hip, bm/dataset.py:349-364, 263-278, 172-175): windows gathered out of
+# recordings that stay resident on the device.
+class SegmentTable:
+    """The device table of ``bm_segment_gather`` for one array per recording (``[rows_r, n_r]``, fp32 or bool, read in
+    place: the table keeps the tensors alive)."""
+
+    def __init__(self, arrays: tp.Sequence[torch.Tensor]):
+        L = lib()
+        if not arrays:
+            raise BmHipError("segment table: no recording")
+        self.dtype, self.device = arrays[0].dtype, arrays[0].device
+        if self.dtype not in (torch.float32, torch.bool):
+            raise BmHipError(f"segment table: fp32 or bool, got {self.dtype}")
+        entry = L.bm_segment_table_entry_bytes()
+        host = torch.zeros(len(arrays), entry, dtype=torch.uint8)
+        for i, a in enumerate(arrays):
+            _req(a, f"segment table: recording {i}", self.dtype)
+            if a.dim() != 2 or a.device != self.device:
+                raise BmHipError(f"segment table: recording {i} of shape {tuple(a.shape)} on {a.device}")
+            check(L.bm_segment_table_fill(ctypes.c_void_p(host[i].data_ptr()), _p(a), a.shape[1], a.shape[0]),
+                  "bm_segment_table_fill")
+        self.arrays = list(arrays)
+        self.table = host.to(self.device)
+
+    def __len__(self) -> int:
+        return len(self.arrays)
+
+
+def segment_gather(table: SegmentTable, rec: torch.Tensor, start: torch.Tensor, first: int, count: int, channels: int,
+                   T: int, flag: torch.Tensor, baseline: tp.Optional[tp.Tuple[int, int]] = None,
+                   dest: tp.Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``[count, channels, T]``: segment ``b`` is the window ``start[first + b] ... + T - 1`` of recording
+    ``rec[first + b]``, rows beyond the recording's are +0.0.  ``rec`` / ``start``: int32 device arrays (a whole epoch;
+    the batch is an offset, nothing is copied).  ``baseline`` = (first, last) window sample, inclusive: the fp64 mean of
+    those samples is subtracted (fp32 only).  ``flag``: one int32 on the device, set to 1 when a segment is out of range
+    (that segment is +0.0).  ``dest``: write into this contiguous tensor instead of a new one."""
+    _req(rec, "segment_gather.rec", torch.int32)
+    _req(start, "segment_gather.start", torch.int32)
+    _req(flag, "segment_gather.flag", torch.int32)
+    if rec.numel() != start.numel() or flag.numel() < 1:
+        raise BmHipError("segment_gather: rec and start differ in length, or the flag is empty")
+    base0, base1 = (-1, -1) if baseline is None else (int(baseline[0]), int(baseline[1]))
+    if dest is None:
+        dest = torch.empty(count, channels, T, device=table.device, dtype=table.dtype)
+    else:
+        _req(dest, "segment_gather.dest", table.dtype)
+        if tuple(dest.shape) != (count, channels, T):
+            raise BmHipError(f"segment_gather: dest is {tuple(dest.shape)}, the batch is {(count, channels, T)}")
+        _touched(dest)
+
+    def launch():
+        check(lib().bm_segment_gather(_p(table.table), len(table), _p(rec), _p(start), rec.numel(), first, count,
+                                      channels, T, base0, base1, dest.element_size(), _p(dest), _p(flag), _stream()),
+              "bm_segment_gather")
+    _timed("segment_gather", 0., launch)
+    return dest

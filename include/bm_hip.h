@@ -417,6 +417,30 @@ int bm_spectral_fwd(const void* table, int nmat, int max_slabs, const float* R, 
 int bm_spectral_bwd(const void* table, int nmat, int max_slabs, int max_tiles, int niters, float* ws_floats,
                     double* ws_doubles, const float* gscale, float* grads, void* stream);
 
+/* ---- the data loader's batch (segments.hip)  bm/dataset.py:349-364, 263-278, 172-175 ----
+ * SegmentDataset.__getitem__ + SegmentBatch.collate_fn + the baseline correction of mne.Epochs(..., baseline=...) as ONE
+ * launch per tensor over recordings that are resident on the device:
+ *     dst[b][c][t] = src_r[c][start_b + t] - mean_b,c   for c < rows_r,   +0.0 for rows_r <= c < C (the F.pad to
+ * meg_dimension, bm/dataset.py:353-354), with r = rec[first + b], start_b = start[first + b].
+ * table: R entries (bm_segment_table_entry_bytes bytes each, filled on the host by bm_segment_table_fill, then copied to
+ * the device): the address of a recording's [rows][n] array (unit stride inside a row, n elements between rows), n and
+ * rows -- the recordings are read in place.  rec / start: int32 [n_index] on the device, the arrays of a whole epoch;
+ * a batch is the B segments from `first` on.  elem_bytes 4 (fp32) or 1 (bytes: the features mask).
+ * Baseline (fp32 only): base0 < 0 = none, the source bits pass through; else mean_b,c is the fp64 sum of the row's
+ * window samples base0..base1 (inclusive, 0 <= base0 <= base1 < T) in ascending t, divided once, and the difference is
+ * taken in fp64 and rounded once -- one order: the same bits on every grid, alone or among other segments.  A NaN
+ * inside the baseline window makes the row NaN.
+ * A rec outside [0, R) or a start outside [0, n - T] is checked BEFORE any address is formed: the whole segment is
+ * +0.0 and *flag (one int32 on the device, the caller's) is set to 1 by a plain store.  dst: contiguous [B][C][T],
+ * 4-byte aligned (16-byte stores are used wherever the flat output allows), every element written exactly once.
+ * fp32: T <= 4096, else BM_ERR_UNSUPPORTED; B * C * T < 2^31.  No atomics, no scratch; B == 0 returns without a launch.
+ * The byte path is sized for the one-row mask of the reference: one byte per thread, the segment re-checked per byte;
+ * correct for any C, slow for a wide one. */
+long bm_segment_table_entry_bytes(void);
+int bm_segment_table_fill(void* entry, const void* base, long n, int rows);
+int bm_segment_gather(const void* table, int R, const int* rec, const int* start, long n_index, long first, int B, int C,
+                      int T, int base0, int base1, int elem_bytes, void* dst, int* flag, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
