@@ -10,7 +10,7 @@ __global__ __launch_bounds__(256) void inv_norms_kernel(const float* __restrict_
     __shared__ double sh[4];
     const float* row = cand + (long)blockIdx.x * K;
     double s = 0;
-    if ((K & 3) == 0) {
+    if ((K & 3) == 0 && (((uintptr_t)row & 15) == 0)) {      // the predicate of cand_prep_kernel: the same order at any base
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
         for (long i = threadIdx.x; i < K / 4; i += blockDim.x) {
             const float4 v = reinterpret_cast<const float4*>(row)[i];

@@ -1,9 +1,9 @@
 // HBM-bound epilogue kernels of the ConvSequence block (bm/models/common.py:113-151):
 // BatchNorm1d (train: batch statistics over (B,T); eval: running statistics), GELU/ReLU/LeakyReLU,
 // residual add, GLU -- forward and backward.  All tensors are fp32 [B][C][T] with T contiguous;
-// every kernel streams rows with 16-byte accesses when T % 4 == 0 (the 360-sample case) and falls
-// back to dword accesses otherwise (T = 343 / 361 ...).  Channel reductions are two-stage
-// (per-(channel, split) partials in a fixed order -> deterministic).
+// every kernel streams rows with 16-byte accesses when T % 4 == 0 (the 360-sample case) and its pointers are
+// 16-byte aligned, and falls back to dword accesses otherwise (T = 343 / 361 ..., a view 4 bytes into a buffer).
+// Channel reductions are two-stage (per-(channel, split) partials in a fixed order -> deterministic).
 #include <cstdlib>
 #include "bm_common.h"
 
@@ -28,6 +28,11 @@ template <> struct Pack<4> {
         if (vec4) hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, stream, __VA_ARGS__);        \
         else hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);             \
     } while (0)
+// host: every pointer a kernel dereferences as a float4 is 16-byte aligned (a null one does not count against it); the
+// C ABI asks for 4-byte alignment only, so the 16-byte form is taken on the shape AND the pointers
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
 // host: workgroups of 256 threads of a flat grid-stride kernel over n items
 static int flat_blocks(long n) { return (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256); }
 
@@ -249,7 +254,7 @@ extern "C" int bm_affine_act_res(const float* y, const float* scale, const float
     BM_REQUIRE(n < 0xffffffffL, "affine_act_res: tensor of %ld elements (32-bit element index)", n);
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    const int vec = T % 4 == 0 ? 4 : 1;
+    const int vec = T % 4 == 0 && aligned16(y, res, out) ? 4 : 1;
     const long nvec = n / vec;
     const int nblk = flat_blocks(nvec);
     LAUNCH_VEC(vec == 4, affine_act_res_kernel, dim3(nblk), s, y, scale, shift, res, out, nvec, C, T, act, leak, amax_dst,
@@ -646,7 +651,9 @@ extern "C" int bm_act_bn_bwd(const float* dout, const float* y, const float* sca
     if ((long)B * C * T == 0) return BM_OK;
     const bool reduce = bn_train || (scale && (dgamma || dbeta));
     int maxit = 0;
-    const int nfused = (reduce && scale && shift && mean && invstd) ? fused_nsplit(B, C, T, &maxit) : 0;
+    // the one-pass kernel reads and writes float4 only: taken where the shape is covered and the pointers allow
+    const bool vec4 = T % 4 == 0 && aligned16(dout, y, dy);
+    const int nfused = (vec4 && reduce && scale && shift && mean && invstd) ? fused_nsplit(B, C, T, &maxit) : 0;
     const int nsplit = nfused ? nfused : bm_bwd_nsplit(B);
     if (workspace_bytes < bm_act_bn_bwd_workspace_bytes(B, C))
         return bm_set_error(BM_ERR_WORKSPACE, "act_bn_bwd: workspace too small (%ld < %ld)", workspace_bytes,
@@ -667,9 +674,9 @@ extern "C" int bm_act_bn_bwd(const float* dout, const float* y, const float* sca
                            leak, amax_dst, bm_fastdiv((unsigned)(T / 4)), bm_fastdiv((unsigned)nsplit), g_fused_poll_limit);
     } else {
         if (reduce)
-            LAUNCH_VEC(T % 4 == 0, bn_bwd_reduce_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, B, C, T,
+            LAUNCH_VEC(vec4, bn_bwd_reduce_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, B, C, T,
                        act, leak);
-        LAUNCH_VEC(T % 4 == 0, bn_bwd_apply_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, bn_train, dy,
+        LAUNCH_VEC(vec4, bn_bwd_apply_kernel, grid, s, dout, y, scale, shift, mean, invstd, partial, bn_train, dy,
                    dy_partial, dgamma, dbeta, B, C, T, act, leak, amax_dst, 1);
     }
     return finish_rows("act_bn_bwd", amax_dst, C, nsplit, C * nsplit, amax_out, amax_rows_out, dy_partial, dbias, s);
@@ -708,7 +715,8 @@ extern "C" int bm_channel_sum(const float* x, long bstride, float* out, void* wo
         return bm_set_error(BM_ERR_WORKSPACE, "channel_sum: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     double* partial = (double*)workspace;
-    LAUNCH_VEC(T % 4 == 0 && bstride % 4 == 0, channel_sum_kernel, dim3(C, nsplit), s, x, bstride, partial, B, C, T);
+    LAUNCH_VEC(T % 4 == 0 && bstride % 4 == 0 && aligned16(x), channel_sum_kernel, dim3(C, nsplit), s, x, bstride, partial,
+               B, C, T);
     hipLaunchKernelGGL(finalize_channel_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, partial, out, C,
                        nsplit);
     return bm_check_launch("channel_sum");
@@ -775,7 +783,7 @@ extern "C" int bm_channel_stats(const float* x, float* stats, int B, int C, int 
     BM_REQUIRE(x && stats, "channel_stats: null pointer");
     const int nsplit = bm_channel_stats_splits(B);
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH_VEC(T % 4 == 0, channel_stats_kernel, dim3(C, nsplit), s, x, stats, B, C, T);
+    LAUNCH_VEC(T % 4 == 0 && aligned16(x), channel_stats_kernel, dim3(C, nsplit), s, x, stats, B, C, T);
     return bm_check_launch("channel_stats");
 }
 
@@ -813,7 +821,7 @@ extern "C" int bm_glu_fwd(const float* u, float* out, int B, int H, int T, float
     BM_REQUIRE(n < 0xffffffffL && (long)H * T < 0xffffffffL, "glu_fwd: tensor of %ld elements (32-bit element index)", n);
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    const int vec = T % 4 == 0 ? 4 : 1;
+    const int vec = T % 4 == 0 && aligned16(u, out) ? 4 : 1;
     const long nvec = n / vec;
     const int nblk = flat_blocks(nvec);
     LAUNCH_VEC(vec == 4, glu_fwd_kernel, dim3(nblk), s, u, out, nvec, H, T, amax_dst,
@@ -891,6 +899,7 @@ extern "C" int bm_glu_bwd(const float* dout, const float* u, float* du, float* d
     double* partial = (double*)workspace;
     hipStream_t s = (hipStream_t)stream;
     const BmAmaxDst amax_dst = bm_amax_dst(amax_out, amax_ws);
-    LAUNCH_VEC(T % 4 == 0, glu_bwd_kernel, dim3(H, nsplit), s, dout, u, du, partial, B, H, T, amax_dst);
+    LAUNCH_VEC(T % 4 == 0 && aligned16(dout, u, du), glu_bwd_kernel, dim3(H, nsplit), s, dout, u, du, partial, B, H, T,
+               amax_dst);
     return finish_rows("glu_bwd", amax_dst, 2 * H, nsplit, H * nsplit, amax_out, amax_rows_out, partial, dbias, s);
 }

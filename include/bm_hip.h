@@ -10,6 +10,7 @@
  *     available (thread-local) from bm_last_error().  Nothing aborts or throws across the ABI.
  *   - all tensors are fp32, contiguous, [B][channels][T] with T fastest, living in device memory
  *     owned by the caller.  Indices are int32 (widx, order, seg) or int64 (idx of group_by_index).
+ *   - every fp32 pointer needs 4-byte alignment only; the 16-byte paths are taken where the pointers allow.
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); kernels are
  *     only enqueued, never synchronised.  The library allocates nothing; scratch is caller-provided.
  *   - deterministic: every reduction has a fixed order (split-K partials are folded in order).
@@ -242,7 +243,7 @@ long bm_act_bn_bwd_workspace_bytes(int B, int C);
 int bm_act_bn_bwd_set_fused(int mode);                    /* 0: two passes; 1: one pass (-1: default = 1 unless BM_BN_BWD_FUSED=0); returns the previous setting */
 int bm_act_bn_bwd_set_poll_limit(int polls);              /* test hook: polls before a workgroup computes its partners' sums itself (-1: default) */
 long bm_act_bn_bwd_fused_fallbacks(void);                 /* debug counter (synchronises): workgroups of the one-pass kernel that gave up on a partner and computed its sums themselves */
-int bm_act_bn_bwd_fused_covers(int B, int C, int T);      /* 1: train-mode BatchNorm backward runs as ONE pass (slab in registers) */
+int bm_act_bn_bwd_fused_covers(int B, int C, int T);      /* 1: the shape is covered by the ONE-pass train-mode BatchNorm backward (slab in registers); taken when dout, y and dy are 16-byte aligned too */
 int bm_act_bn_bwd(const float* dout, const float* y, const float* scale, const float* shift,
                   const float* mean, const float* invstd, int bn_train, float* dy, float* dgamma,
                   float* dbeta, float* dbias, void* workspace, long workspace_bytes, int B, int C,

@@ -46,6 +46,45 @@ def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
     return (a - b).norm().item() / denom
 
 
+def shifted(t: torch.Tensor, k: int) -> torch.Tensor:
+    """``t`` on the GPU as the view ``buf[k:k + n].view(t.shape)`` of a flat fp32 buffer: contiguous, its base ``4 * k``
+    bytes past a 16-byte boundary (k in 0..3; k = 0: an aligned view, the same code path on the test's side)."""
+    assert 0 <= k <= 3 and t.dtype == torch.float32 and t.numel() > 0
+    n = t.numel()
+    buf = torch.empty(n + 3, device="cuda", dtype=torch.float32)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[k:k + n].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4 * k and view.is_contiguous()
+    return view
+
+
+class ShiftedOut:
+    """A NaN-poisoned fp32 output ``.view`` of ``shape``, ``4 * k`` bytes past a 16-byte boundary, inside a buffer that
+    holds ``guard`` canary floats in front of it and behind it (tests/test_guard_bands_gpu.py's layout).  ``check`` after
+    the kernel: every canary intact (no store left the view -- one element past a gradient view is the neighbouring
+    parameter's gradient) and no NaN left (no element skipped)."""
+    CANARY = -7.0e37
+
+    def __init__(self, shape, k: int, guard: int = 1024):
+        assert 0 <= k <= 3 and guard % 4 == 0
+        n = 1
+        for s in shape:
+            n *= int(s)
+        assert n > 0
+        self.buf = torch.full((guard + k + n + guard,), self.CANARY, device="cuda", dtype=torch.float32)
+        assert self.buf.data_ptr() % 16 == 0
+        self.lo, self.hi = guard + k, guard + k + n
+        self.view = self.buf[self.lo:self.hi].view(tuple(shape))
+        self.view.fill_(float("nan"))
+        assert self.view.data_ptr() % 16 == 4 * k and self.view.is_contiguous()
+
+    def check(self, what):
+        assert bool((self.buf[:self.lo] == self.CANARY).all()), f"{what}: a store landed BELOW the view"
+        assert bool((self.buf[self.hi:] == self.CANARY).all()), f"{what}: a store landed ABOVE the view"
+        assert not bool(torch.isnan(self.view).any()), f"{what}: NaN left in the output (a skipped element)"
+
+
 NOISE = 1e-6
 
 

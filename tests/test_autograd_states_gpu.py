@@ -1,6 +1,7 @@
 """The autograd glue (brainmagick_amd/functional.py) in the states a training step never makes: every Function against
 fp64 torch autograd on the CPU with subsets of its inputs requiring grad, non-contiguous operands and incoming
-gradients, a graph that is used twice, outputs consumed one at a time, and no tape at all.
+gradients, operands and gradients 4, 8 and 12 bytes off their 16-byte alignment, a graph that is used twice, outputs
+consumed one at a time, and no tape at all.
 
 Reference: the same operation restated with torch ops in float64 (F.conv1d / F.conv_transpose1d / F.batch_norm / F.gelu
 / F.glu / nn.LSTM / einsum, oracle.bm_oracle for the merger, the composed front end and ClipLoss, the fp64 forms of
@@ -23,7 +24,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import close, rel_l2
+from helpers import close, rel_l2, shifted
 from oracle import bm_oracle as O
 import test_feature_decoding_gpu as TFD
 
@@ -492,6 +493,98 @@ def test_non_contiguous_incoming_gradients_change_no_bit(H, mode, name, grad):
         sum((o.transpose(1, 2).contiguous() if o.dim() >= 3 else o).square().sum() for o in outs).backward()
     for k in case.inputs:
         assert torch.equal(t[k].grad, base[k].grad), (name, k)
+
+
+# ---- operands off their 16-byte alignment -----------------------------------------------------------------------------------
+# Every input of two or more dimensions and every incoming gradient is a contiguous view 4, 8 or 12 bytes past a 16-byte
+# boundary of a flat buffer (helpers.shifted): what a parameter is in FlatAdam's bucket behind one with numel % 4 != 0,
+# and an activation that is a slice of a larger buffer.  Held to fp64 like every other state, and to the bits of the
+# aligned run: the convs and contractions stage a shifted operand differently and multiply alike, the elementwise
+# kernels compute each element alike.  What may differ is a per-channel SUM taken by a streaming kernel that reads
+# 16-byte vectors behind aligned pointers and dwords otherwise (T % 4 == 0 only): the two walks add in different orders.
+WIDE_T = (192, 132)
+WIDE_NAMES = {f"wide-{Tn}-{idx}": (Tn, idx) for Tn in WIDE_T for idx in range(5)}
+
+# case -> (the gradients that are NOT held to the aligned run's bits, the kernel whose sum they are or hang on, the two
+# paths).  Everything else of these cases -- the output, the data gradient, the weight gradient -- IS held to the bits.
+_SUM = "csrc/norm_act.hip channel_sum_kernel<4> (a thread adds the four lanes of every 256th vector) / <1> (every 256th sample)"
+_BWD = ("csrc/norm_act.hip bn_bwd_apply_kernel<4> / <1>: dy is elementwise and equal, its per-channel sum (dbias) is "
+        "folded per thread over vectors / over samples")
+_BN = ("csrc/norm_act.hip bn_bwd_fused_kernel (one pass, float4, behind aligned dout / pre) / bn_bwd_reduce_kernel<1> + "
+       "bn_bwd_apply_kernel<1> (two passes, dwords): the per-channel sums of dz and dz * xhat")
+_GLU = "csrc/norm_act.hip glu_bwd_kernel<4> / <1>: du is elementwise and equal, its per-channel sum (dbias) is not"
+BITS_EXEMPT = {
+    f"conv1d-thead-none-{C}x{M}x{T}": (("b",), _SUM),                 # dbias = channel_sum(dout), dout shifted
+    f"conv1d-strided-gelu-{C}x{M}x{T}": (("b",), _BWD),               # act_bn_bwd without BatchNorm: no sums feed dy
+    f"convbn-eval-nores-{C}x{M}x{T}": (("b", "gamma", "beta"), _BN),  # eval: dy = scale * dz needs no sum
+    "wide-192-0": (("b",), _BWD), "wide-132-0": (("b",), _BWD),       # conv1d-same-gelu
+    "wide-192-1": (("b",), _SUM), "wide-132-1": (("b",), _SUM),       # conv1d-thead-none
+    # train-mode BatchNorm: dy subtracts the channel means of dz and dz * xhat, so x and w hang on the sums too
+    "wide-192-2": (("x", "w", "b", "gamma", "beta"), _BN), "wide-132-2": (("x", "w", "b", "gamma", "beta"), _BN),
+    "wide-192-3": (("b", "gamma", "beta"), _BN), "wide-132-3": (("b", "gamma", "beta"), _BN),     # convbn-eval-nores
+    "wide-192-4": (("b",), _GLU), "wide-132-4": (("b",), _GLU),       # glu
+}
+# the cases held to the aligned run's bits in every tensor (T = 49: every kernel takes its dword path either way)
+BITS_EQUAL = [n for n in NONCONTIG + list(WIDE_NAMES) if n not in BITS_EXEMPT]
+ALIGNMENT_IDS = [(m, n) for n in NONCONTIG for m in MODES] + [("f16x2", n) for n in WIDE_NAMES]
+
+
+def _alignment_case(name):
+    if name not in WIDE_NAMES:
+        return _case(name)
+    Tn, idx = WIDE_NAMES[name]
+    if Tn not in _WIDE:
+        _WIDE[Tn] = _wide_cases(Tn)
+    return _WIDE[Tn][idx]
+
+
+def _shifted_leaves(case, k):
+    """(leaves, tensors handed to the Function, leaf gradient -> gradient in the input's own layout), as ``_views``:
+    every input of two or more dimensions is a leaf that is itself the view buf[k:k + n] of a flat buffer."""
+    leaves, used, back = {}, {}, {}
+    for name, v in case.inputs.items():
+        leaves[name] = (shifted(v, k) if v.dim() >= 2 else v.cuda()).requires_grad_(True)
+        assert leaves[name].is_leaf and (v.dim() < 2 or leaves[name].data_ptr() % 16 == 4 * k)
+        used[name], back[name] = leaves[name], lambda g: g
+    return leaves, used, back
+
+
+def test_the_bit_equality_exemptions_are_sums_of_the_streaming_kernels():
+    """The exemption list holds per-channel sums of norm_act.hip only: no output, and a data or weight gradient only
+    where train-mode BatchNorm feeds the sums back into dy."""
+    assert set(BITS_EXEMPT) | set(BITS_EQUAL) == set(NONCONTIG) | set(WIDE_NAMES) and not set(BITS_EXEMPT) & set(BITS_EQUAL)
+    for name, (tensors, why) in BITS_EXEMPT.items():
+        case = _alignment_case(name)
+        assert "csrc/norm_act.hip" in why and set(tensors) <= set(case.inputs), name
+        assert case.inputs["x"].shape[-1] % 4 == 0, (name, "no 16-byte path to differ from")
+        if set(tensors) & {"x", "w"}:
+            assert case.name.startswith("convbn-train"), name
+    print(f"bit-equality exemptions: {len(BITS_EXEMPT)} of {len(BITS_EXEMPT) + len(BITS_EQUAL)} cases, "
+          f"{sum(len(t) for t, _ in BITS_EXEMPT.values())} gradients")
+
+
+@pytest.mark.parametrize("mode,name", ALIGNMENT_IDS, indirect=["mode"], ids=[f"{n}-{m}" for m, n in ALIGNMENT_IDS])
+def test_operands_off_16_byte_alignment(H, mode, name):
+    """Shifts of 4, 8 and 12 bytes, applied to all tensors at once: outputs and every gradient against fp64, and
+    against the bits of the aligned run but for ``BITS_EXEMPT``."""
+    case = _alignment_case(name)
+    exempt = set(BITS_EXEMPT[name][0]) if name in BITS_EXEMPT else set()
+    dys = case.reference()[1]
+    base = _leaves(case, tuple(case.inputs))
+    base_outs, labels = _launches(H, lambda: _step(case, base, dys))
+    if name in WIDE_NAMES:
+        assert any(n.startswith("conv_nn_h2w") for n in labels) and any(n.startswith("gemm_nt_h2w") for n in labels), labels
+    for k in (1, 2, 3):
+        leaves, used, back = _shifted_leaves(case, k)
+        outs = case.hip(used)
+        torch.autograd.backward(outs, [shifted(d, k) if d.dim() else d.cuda() for d in dys])
+        grads = {n: back[n](leaves[n].grad) for n in case.inputs}
+        _check_against_fp64(case, outs, grads, tuple(case.inputs))
+        for a, b in zip(outs, base_outs):
+            assert torch.equal(a, b), (name, k, "output")
+        for n in case.inputs:
+            if n not in exempt:
+                assert torch.equal(grads[n], base[n].grad), (name, k, n, rel_l2(grads[n], base[n].grad))
 
 
 # ---- a graph used more than once ----------------------------------------------------------------------------------------

@@ -1599,3 +1599,87 @@ def test_negative_pool_completes_the_candidates_like_the_reference():
         assert torch.equal(solver.negative_pool["train"].cpu(), buf), k
         loss = solver.loss(estimate, completed, mask)
         assert abs(float(loss) - float(O.clip_loss(estimate.cpu(), out_ref))) < LOSS_TOL
+
+
+@pytest.mark.parametrize("penalty", [False, True], ids=["clip", "clip+svd"])
+@pytest.mark.parametrize("dtype", ["f16x2", "f32"])
+def test_parameter_bucket_at_every_phase(dtype, penalty):
+    """FlatAdam packs parameters and gradients without padding, so a parameter starts wherever the ones in front of it
+    end: a ``k``-element parameter in front of the model's (k = 0..3, outside the graph) moves every weight, bias and
+    gradient view by 4 k bytes, through all four phases of a 16-byte boundary.  The kernels read the weights in place,
+    the weight-gradient kernels store straight into the bucket views (``grad_destination``), ``spectral.hip`` reads
+    the matrices in place (``penalty``: with ``svd_penalty`` over the model's weights).  One training step per k from
+    the same weights: loss, estimate, every gradient, both Adam moments and every updated parameter are the same bits
+    whatever k -- no kernel chooses a path, or a summation order, by a parameter's address.  The k = 0 run meets the
+    CPU oracle (which has no penalty: with it only the estimate is held to the oracle)."""
+    from brainmagick_amd import hip_ops as H
+    from brainmagick_amd.losses import ClipLoss
+    from brainmagick_amd.optim import FlatAdam
+    from brainmagick_amd.svd import penalized_weights, svd_penalty
+    B, C, T, Fd, S, hidden = 12, 20, 48, 10, 3, 32
+    sb = synthetic.make_batch(B, C, T, Fd, S, n_layouts=2)
+    sbg = sb.to("cuda")
+    model0, cfg = _small_model(merger_dropout=0.0)
+    sd0 = copy.deepcopy(model0.state_dict())
+    gen = torch.Generator().manual_seed(17)
+    mats = [torch.randn(min(w.shape[0], w.numel() // w.shape[0]), 16, generator=gen)
+            for _, w in penalized_weights(model0)]
+    assert len(mats) >= 5
+    runs = []
+    H.set_compute_dtype(dtype)
+    try:
+        for k in range(4):
+            model, _ = _small_model(merger_dropout=0.0)
+            model.load_state_dict(sd0)
+            model = model.cuda().train()
+            pad = [torch.nn.Parameter(torch.zeros(k, device="cuda"))] if k else []
+            opt = FlatAdam(pad + list(model.parameters()), lr=3e-4, betas=(0.9, 0.999))
+            named = dict(model.named_parameters())
+            assert opt.flat_param.data_ptr() % 16 == 0 and opt.flat_grad.data_ptr() % 16 == 0
+            opt.zero_grad(set_to_none=True)
+            est = model({"meg": sbg.meg.clone()}, sbg)
+            loss = ClipLoss().cuda().train()(est, sbg.features, sbg.features_mask)
+            if penalty:
+                loss = loss + 0.1 * svd_penalty(model, test_matrices=mats)
+            with opt.writing_grads():
+                loss.backward()
+            where = {n: (p.data_ptr() - opt.flat_param.data_ptr(), p.grad.data_ptr() - opt.flat_grad.data_ptr())
+                     for n, p in named.items()}
+            # the weight-gradient kernels stored straight into the bucket views: handed out by grad_destination, and
+            # (without the penalty, which uses every matrix a second time and so makes autograd add) adopted as p.grad
+            handed = [n for n, p in named.items() if p.dim() > 1 and p._bm_grad_dst[1][0]]
+            direct = [n for n in handed if where[n][1] == where[n][0]]
+            assert handed and (penalty or direct), "no weight gradient was written straight into the bucket"
+            opt.step()
+            for n, p in named.items():          # after the step every gradient is its view of the bucket
+                assert p.grad.data_ptr() - opt.flat_grad.data_ptr() == where[n][0], n
+            torch.cuda.synchronize()
+            runs.append(dict(where=where, loss=loss.detach().clone(), est=est.detach().clone(),
+                             grad={n: p.grad.clone() for n, p in named.items()},
+                             m1={n: opt.state[p]["exp_avg"].clone() for n, p in named.items()},
+                             m2={n: opt.state[p]["exp_avg_sq"].clone() for n, p in named.items()},
+                             param={n: p.detach().clone() for n, p in named.items()}))
+    finally:
+        H.set_compute_dtype(H.DEFAULT_COMPUTE_DTYPE)
+    base = runs[0]
+    # the weights of the k = 0 run already sit at more than one phase, and every k moves all of them by 4 k bytes
+    assert len({off % 16 for n, (off, _) in base["where"].items() if base["param"][n].dim() > 1}) > 1
+    for k, run in enumerate(runs):
+        for n, (off, _) in run["where"].items():
+            assert off == base["where"][n][0] + 4 * k, (k, n)
+    for k, run in enumerate(runs[1:], 1):
+        assert torch.equal(run["loss"], base["loss"]), (k, float(run["loss"]), float(base["loss"]))
+        assert torch.equal(run["est"], base["est"]), k
+        for what in ("grad", "m1", "m2", "param"):
+            for n in base[what]:
+                assert torch.equal(run[what][n], base[what][n]), \
+                    (f"{what} of {n} differs in bits with the bucket moved by {4 * k} bytes: "
+                     f"rel-L2 {rel_l2(run[what][n], base[what][n]):.3e}")
+    oracle = O.OracleModel(copy.deepcopy(sd0), cfg, hidden, Fd)
+    loss_ref, est_ref, grads_ref = oracle.loss_and_grads(sb.meg, sb.positions(), sb.subject_index, sb.features, True)
+    assert rel_l2(base["est"], est_ref) < FWD_TOL, rel_l2(base["est"], est_ref)
+    if not penalty:
+        assert abs(float(base["loss"]) - float(loss_ref)) < LOSS_TOL
+        gscale = max(v.double().norm().item() for v in grads_ref.values())
+        for n, g in base["grad"].items():
+            assert close(g, grads_ref[n], GRAD_TOL, gscale), (n, rel_l2(g, grads_ref[n]))
