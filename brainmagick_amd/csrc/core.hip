@@ -20,7 +20,7 @@ int bm_check_launch(const char* what) {
 }
 
 extern "C" const char* bm_last_error(void) { return bm_err_buf; }
-extern "C" int bm_version(void) { return 112; }   // 0.1.12: the segment loader (bm_segment_*)
+extern "C" int bm_version(void) { return 113; }   // 0.1.13: the features builder (bm_segment_features)
 
 // Number of HIP devices visible; <0 on error.  Lets the Python side fail loudly early.
 extern "C" int bm_device_count(void) {

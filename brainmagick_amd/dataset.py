@@ -13,8 +13,13 @@ sample)`` arrays of the epoch, which are uploaded once per epoch.
 - ``DeviceRecording``, ``DeviceSegments``, ``DeviceSegmentLoader``: the dataset and its loader; torch's own samplers
   decide the order, the loader only replaces what they index.
 
-Not built: the events-to-features builders (the caller hands full-length feature arrays), ``autoreject``,
-``split_wav_as_block``, ``decim != 1``, channel picking, resampling / ``highpass``.  There is no CPU fallback.
+The features of a batch come either from full-length arrays (two more gathers) or from the recording's events
+(``DeviceRecording(meg, events=features.DeviceEvents(...))``): then ONE ``hip_ops.segment_features`` launch builds the
+features and the mask of the batch by the reference's per-window rules (features.py, csrc/features.hip).
+
+Not built: WordPulse / PhonemePulse (``post_process``), Wav2VecChunk, the batch's ``_event_lists``, computing the mel
+spectrogram / wav2vec2 / embeddings themselves, ``autoreject``, ``split_wav_as_block``, ``decim != 1``, channel picking,
+resampling / ``highpass``.  There is no CPU fallback.
 """
 import copy
 import typing as tp
@@ -124,17 +129,26 @@ def raise_if_range_error(device) -> None:
 
 class DeviceRecording:
     """One preprocessed recording on the device.  ``meg``: [C_r, N] fp32, ``features``: [F, N] fp32, ``features_mask``:
-    [M, N] bool; a tensor that is already there is adopted without a copy.  ``recording``: anything with
-    ``recording_index`` and ``layout`` (``synthetic.Recording``)."""
+    [M, N] bool; a tensor that is already there is adopted without a copy.  ``events`` (``features.DeviceEvents``)
+    instead of ``features`` / ``features_mask``: the features and the mask of a batch are built from the events by
+    ``hip_ops.segment_features``.  ``recording``: anything with ``recording_index`` and ``layout``
+    (``synthetic.Recording``)."""
 
-    def __init__(self, meg, features=None, features_mask=None, *, recording, subject_index: int, device=None):
+    def __init__(self, meg, features=None, features_mask=None, *, recording, subject_index: int, device=None,
+                 events=None):
         self.recording = recording
         self.subject_index = int(subject_index)
         self.recording_index = int(recording.recording_index)
+        if events is not None and (features is not None or features_mask is not None):
+            raise ValueError("a recording carries either its events (the features are built per batch) or full-length "
+                             "features / features_mask arrays, not both")
         if device is None:
             device = meg.device if isinstance(meg, torch.Tensor) and meg.is_cuda else \
                 torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
         self.meg = self._adopt(meg, torch.float32, device)
+        self.events = events                                        # features.DeviceEvents, or None
+        if events is not None and events.device.type != self.meg.device.type:
+            raise ValueError(f"the events are on {events.device}, the MEG on {self.meg.device}")
         self.features = None if features is None else self._adopt(features, torch.float32, device)
         self.features_mask = None if features_mask is None else self._adopt(features_mask, torch.bool, device)
         for name in ("features", "features_mask"):
@@ -189,12 +203,26 @@ class DeviceSegments:
             assert meg_dimension >= r.n_channels                               # bm/dataset.py:321
         self.meg_dimension = meg_dimension
         first = self.recordings[0]
+        with_events = [r.events is not None for r in self.recordings]
+        if any(with_events) and not all(with_events):
+            raise ValueError("some recordings carry events and others full-length arrays: "
+                             f"{['events' if e else 'arrays' for e in with_events]}")
+        self.builder = first.events.builder if with_events[0] else None
+        if self.builder is not None:
+            if any(r.events.builder is not self.builder for r in self.recordings):
+                raise ValueError("the recordings' events were made for different features builders")
+            if self.builder.sample_rate != self.sample_rate:
+                raise ValueError(f"the features builder samples at {self.builder.sample_rate} Hz, the segments at "
+                                 f"{self.sample_rate} Hz")
         for name in ("features", "features_mask"):
             shapes = {None if getattr(r, name) is None else getattr(r, name).shape[0] for r in self.recordings}
             if len(shapes) != 1:
                 raise ValueError(f"the recordings disagree on {name}: {sorted(map(str, shapes))} rows")
-        self.n_features = 0 if first.features is None else first.features.shape[0]
-        self.n_mask = 0 if first.features_mask is None else first.features_mask.shape[0]
+        if self.builder is not None:
+            self.n_features, self.n_mask = self.builder.dimension, 1
+        else:
+            self.n_features = 0 if first.features is None else first.features.shape[0]
+            self.n_mask = 0 if first.features_mask is None else first.features_mask.shape[0]
         rec, start = [], []
         for i, r in enumerate(self.recordings):
             s = segment_starts(r.n_samples, sample_rate, tmin, tmax, condition, _blocks_of(blocks, i, len(self.recordings)),
@@ -207,6 +235,18 @@ class DeviceSegments:
             start.append(s.astype(np.int32))
         self.rec = np.concatenate(rec)
         self.start = np.concatenate(start)
+        self.wstart = self.wdur = None
+        if self.builder is not None:
+            # The window in seconds, as _get_bounds_times hands it to FeaturesBuilder.__call__ (bm/dataset.py:323-344,
+            # bm/features/base.py:77-90): Python's division here, no division on the device.
+            s = self.start.astype(np.int64)
+            self.wstart = s / self.sample_rate
+            self.wdur = (s + self.T) / self.sample_rate - self.wstart
+            n_times = np.round(self.wdur * self.sample_rate).astype(np.int64)
+            if (n_times != self.T).any():
+                i = int(np.flatnonzero(n_times != self.T)[0])
+                raise ValueError(f"segment {i} (first sample {s[i]}): the reference would build {n_times[i]} feature "
+                                 f"samples for a window of {self.T}")
         self._rec_index = np.array([r.recording_index for r in self.recordings], dtype=np.int64)
         self._subject_index = np.array([r.subject_index for r in self.recordings], dtype=np.int64)
         self._tables = None
@@ -224,9 +264,14 @@ class DeviceSegments:
             if not self.device.type == "cuda":
                 raise BmHipError("DeviceSegments: the recordings are not on a GPU; the segment gather is a HIP kernel "
                                  "and has no CPU fallback")
-            self._tables = (H.SegmentTable([r.meg for r in self.recordings]),
-                            H.SegmentTable([r.features for r in self.recordings]) if self.n_features else None,
-                            H.SegmentTable([r.features_mask for r in self.recordings]) if self.n_mask else None)
+            if self.builder is not None:
+                events = H.EventTable(self.builder.plan(), len(self.builder.kinds), self.builder.mask_kind,
+                                      [(r.events.kind_tables, r.events.sources) for r in self.recordings], self.device)
+                self._tables = (H.SegmentTable([r.meg for r in self.recordings]), events, None)
+            else:
+                self._tables = (H.SegmentTable([r.meg for r in self.recordings]),
+                                H.SegmentTable([r.features for r in self.recordings]) if self.n_features else None,
+                                H.SegmentTable([r.features_mask for r in self.recordings]) if self.n_mask else None)
         return self._tables
 
     def upload(self, indices) -> tp.Dict[str, torch.Tensor]:
@@ -237,19 +282,28 @@ class DeviceSegments:
             raise IndexError(f"segment index out of range for {len(self)} segments")
         rec = self.rec[idx]
         dev = self.device
-        return dict(rec=torch.from_numpy(rec).to(dev), start=torch.from_numpy(self.start[idx]).to(dev),
-                    subject_index=torch.from_numpy(self._subject_index[rec]).to(dev),
-                    recording_index=torch.from_numpy(self._rec_index[rec]).to(dev),
-                    recordings=[self.recordings[int(r)].recording for r in rec])
+        arrays = dict(rec=torch.from_numpy(rec).to(dev), start=torch.from_numpy(self.start[idx]).to(dev),
+                      subject_index=torch.from_numpy(self._subject_index[rec]).to(dev),
+                      recording_index=torch.from_numpy(self._rec_index[rec]).to(dev),
+                      recordings=[self.recordings[int(r)].recording for r in rec])
+        if self.builder is not None:
+            arrays.update(wstart=torch.from_numpy(self.wstart[idx]).to(dev), wdur=torch.from_numpy(self.wdur[idx]).to(dev))
+        return arrays
 
     def gather(self, arrays: tp.Dict[str, torch.Tensor], first: int, count: int) -> SegmentBatch:
-        """Segments ``first ... first + count - 1`` of uploaded index arrays: at most three launches, no copy from the
-        host, no synchronisation."""
+        """Segments ``first ... first + count - 1`` of uploaded index arrays: at most three launches (two with events:
+        the MEG gather and the features builder), no copy from the host, no synchronisation."""
         meg_t, feat_t, mask_t = self.tables()
         rec, start = arrays["rec"], arrays["start"]
         flag = range_error_flag(self.device)
         meg = H.segment_gather(meg_t, rec, start, first, count, self.meg_dimension, self.T, flag,
                                baseline=self.baseline)
+        if self.builder is not None:                                   # ONE launch builds the features and the mask
+            features, mask = H.segment_features(feat_t, rec, arrays["wstart"], arrays["wdur"], first, count, self.T,
+                                                self.sample_rate, flag)
+            return SegmentBatch(meg, features, mask, arrays["subject_index"][first:first + count],
+                                arrays["recording_index"][first:first + count],
+                                arrays["recordings"][first:first + count])
         if feat_t is not None:
             features = H.segment_gather(feat_t, rec, start, first, count, self.n_features, self.T, flag)
         else:
@@ -274,6 +328,8 @@ class DeviceSegments:
         sub = copy.copy(self)
         keep = self.rec == recording
         sub.rec, sub.start = self.rec[keep], self.start[keep]
+        if self.builder is not None:
+            sub.wstart, sub.wdur = self.wstart[keep], self.wdur[keep]
         return sub
 
     def per_recording_loaders(self, batch_size: int, generator=None) -> tp.List["DeviceSegmentLoader"]:

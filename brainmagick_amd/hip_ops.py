@@ -8,6 +8,7 @@ fallback path.
 import ctypes
 import typing as tp
 
+import numpy as np
 import torch
 
 from ._lib import lib, check, BmHipError
@@ -1641,3 +1642,128 @@ def segment_gather(table: SegmentTable, rec: torch.Tensor, start: torch.Tensor, 
               "bm_segment_gather")
     _timed("segment_gather", 0., launch)
     return dest
+
+
+# The batch's features from resident events (csrc/features.hip, bm/features/base.py:68-122, 238-267,
+# bm/features/audio.py:78-83, 211-274).
+FEATURE_RULES = {"constant": 0, "resampled": 1, "chunk": 2}
+
+
+class EventTable:
+    """The device tables of ``bm_segment_features``.  ``plan``: one ``(kind slot, rule, first channel, channels, default)``
+    per feature, tiling the channels in order; ``n_kinds`` event kinds; ``mask_kind``: the slot whose events make the mask
+    (-1: all true).  ``recordings``: per recording ``(kinds, sources)`` -- ``kinds``: per slot None (no event) or
+    ``(start, duration, running maximum of start + duration)``, float64 device tensors in painting order; ``sources``: per
+    feature None (no event of its kind), a float32 device tensor ``[n, channels]`` (constant) or ``(arrays, er)``: the
+    events' ``[channels, L]`` float32 device tensors, read in place, and ``L / duration`` of each.  The table keeps every
+    tensor alive."""
+
+    def __init__(self, plan, n_kinds: int, mask_kind: int, recordings, device):
+        L = lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise BmHipError("event table: the events are not on a GPU; the features builder is a HIP kernel and has no "
+                             "CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_features, self.n_kinds, self.mask_kind = len(plan), int(n_kinds), int(mask_kind)
+        self.feat_table = np.ascontiguousarray([[p[0], FEATURE_RULES.get(p[1], p[1]), p[2], p[3]] for p in plan],
+                                               dtype=np.int32).reshape(-1, 4)
+        self.feat_default = np.ascontiguousarray([p[4] for p in plan], dtype=np.float32)
+        self.channels = int(sum(p[3] for p in plan))
+        kb, sb, ab = (L.bm_features_table_entry_bytes(i) for i in range(3))
+        R = len(recordings)
+        kinds = torch.zeros(R, max(self.n_kinds, 1), kb, dtype=torch.uint8)
+        srcs = torch.zeros(R, max(self.n_features, 1), sb, dtype=torch.uint8)
+        self.keep: tp.List[tp.Any] = []
+        for r, (rec_kinds, rec_sources) in enumerate(recordings):
+            if len(rec_kinds) != self.n_kinds or len(rec_sources) != self.n_features:
+                raise BmHipError(f"event table: recording {r} has {len(rec_kinds)} kinds and {len(rec_sources)} sources")
+            counts = []
+            for k, triple in enumerate(rec_kinds):
+                n = 0
+                if triple is not None:
+                    for t in triple:
+                        _req(t, f"event table: recording {r}, kind {k}", torch.float64)
+                    n = triple[0].numel()
+                    if any(t.numel() != n or t.device != self.device for t in triple):
+                        raise BmHipError(f"event table: recording {r}, kind {k}: the event arrays differ in length")
+                    self.keep.append(triple)
+                start, dur, runmax = triple if n else (None, None, None)
+                check(L.bm_features_kind_fill(ctypes.c_void_p(kinds[r, k].data_ptr()), _p(start), _p(dur), _p(runmax), n),
+                      "bm_features_kind_fill")
+                counts.append(n)
+            for f, source in enumerate(rec_sources):
+                slot, rule, _, dim = (int(v) for v in self.feat_table[f])
+                n = counts[slot]
+                if n == 0:
+                    continue                                    # a null source: the kernel finds no event to read it for
+                if rule == 0:
+                    _req(source, f"event table: recording {r}, feature {f}")
+                    if tuple(source.shape) != (n, dim) or source.device != self.device:
+                        raise BmHipError(f"event table: recording {r}, feature {f}: values of shape {tuple(source.shape)} "
+                                         f"for {n} events of {dim} channels")
+                    data = source
+                else:
+                    arrays, ers = source
+                    if len(arrays) != n or len(ers) != n:
+                        raise BmHipError(f"event table: recording {r}, feature {f}: {len(arrays)} arrays for {n} events")
+                    host = torch.zeros(n, ab, dtype=torch.uint8)
+                    for e, (a, er) in enumerate(zip(arrays, ers)):
+                        _req(a, f"event table: recording {r}, feature {f}, event {e}")
+                        if a.dim() != 2 or a.shape[0] != dim or a.device != self.device:
+                            raise BmHipError(f"event table: recording {r}, feature {f}, event {e}: an array of shape "
+                                             f"{tuple(a.shape)} for {dim} channels")
+                        check(L.bm_features_array_fill(ctypes.c_void_p(host[e].data_ptr()), _p(a), a.shape[1], float(er)),
+                              "bm_features_array_fill")
+                    data = host.to(self.device)
+                    self.keep.append(arrays)
+                self.keep.append(data)
+                check(L.bm_features_source_fill(ctypes.c_void_p(srcs[r, f].data_ptr()), _p(data)),
+                      "bm_features_source_fill")
+        self.n_recordings = R
+        self.kinds, self.srcs = kinds.to(self.device), srcs.to(self.device)
+
+    def __len__(self) -> int:
+        return self.n_recordings
+
+
+def segment_features(table: EventTable, rec: torch.Tensor, wstart: torch.Tensor, wdur: torch.Tensor, first: int,
+                     count: int, T: int, sample_rate: float, flag: torch.Tensor,
+                     dest: tp.Optional[torch.Tensor] = None, dest_mask: tp.Optional[torch.Tensor] = None):
+    """``(features [count, F, T] fp32, mask [count, 1, T] bool)`` of the segments ``first ... first + count - 1``: ONE
+    launch that writes every element once.  ``rec`` (int32), ``wstart`` / ``wdur`` (float64: the window's start and
+    duration in seconds): device arrays of a whole epoch.  ``flag``: one int32 on the device, set to 1 when a recording
+    index is out of range (that segment is defaults).  ``dest`` / ``dest_mask``: write into these contiguous tensors."""
+    _req(rec, "segment_features.rec", torch.int32)
+    _req(wstart, "segment_features.wstart", torch.float64)
+    _req(wdur, "segment_features.wdur", torch.float64)
+    _req(flag, "segment_features.flag", torch.int32)
+    if rec.numel() != wstart.numel() or rec.numel() != wdur.numel() or flag.numel() < 1:
+        raise BmHipError("segment_features: rec, wstart and wdur differ in length, or the flag is empty")
+    for name, t in (("rec", rec), ("wstart", wstart), ("wdur", wdur), ("flag", flag), ("dest", dest), ("dest_mask", dest_mask)):
+        if t is not None and t.device != table.device:                 # an address of another card is not one of this one
+            raise BmHipError(f"segment_features: {name} is on {t.device}, the event table on {table.device}")
+    F = table.channels
+    if dest is None:
+        dest = torch.empty(count, F, T, device=table.device, dtype=torch.float32)
+    else:
+        _req(dest, "segment_features.dest")
+        if tuple(dest.shape) != (count, F, T):
+            raise BmHipError(f"segment_features: dest is {tuple(dest.shape)}, the batch is {(count, F, T)}")
+        _touched(dest)
+    if dest_mask is None:
+        dest_mask = torch.empty(count, 1, T, device=table.device, dtype=torch.bool)
+    else:
+        _req(dest_mask, "segment_features.dest_mask", torch.bool)
+        if tuple(dest_mask.shape) != (count, 1, T):
+            raise BmHipError(f"segment_features: dest_mask is {tuple(dest_mask.shape)}, the batch's is {(count, 1, T)}")
+
+    def launch():
+        check(lib().bm_segment_features(ctypes.c_void_p(table.feat_table.ctypes.data),
+                                        ctypes.c_void_p(table.feat_default.ctypes.data), table.n_features, table.n_kinds,
+                                        table.mask_kind, _p(table.kinds), _p(table.srcs), len(table), _p(rec), _p(wstart),
+                                        _p(wdur), rec.numel(), first, count, F, T, float(sample_rate), _p(dest),
+                                        _p(dest_mask), _p(flag), _stream()), "bm_segment_features")
+    _timed("segment_features", 0., launch)
+    return dest, dest_mask

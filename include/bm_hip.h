@@ -442,6 +442,36 @@ int bm_segment_table_fill(void* entry, const void* base, long n, int rows);
 int bm_segment_gather(const void* table, int R, const int* rec, const int* start, long n_index, long first, int B, int C,
                       int T, int base0, int base1, int elem_bytes, void* dst, int* flag, void* stream);
 
+/* ---- the batch's features from resident events (features.hip)  bm/features/base.py:68-122, 238-267 ----
+ * FeaturesBuilder.__call__ with Feature.get_on_overlap, DataSlice.overlap / slice_in_parent (bm/events.py:80-111),
+ * MelSpectrum.get (bm/features/audio.py:78-83) and the Wav2Vec chunk rule (bm/features/audio.py:211-274) as ONE launch per
+ * batch: dst [B][F][T] fp32 and mask [B][1][T] bytes, both contiguous, every element written exactly once; each output is a
+ * copy (a value row, an array entry or a default), the index arithmetic is the reference's in fp64 with rint for round,
+ * uncontracted (the rules are written out at the top of features.hip).
+ * feat_table (HOST memory): NF <= 32 rows {kind, rule, first channel, channels}, tiling [0, F) in order; kind in [0, NK);
+ * rule 0 = constant (one value row per event), 1 = resampled (nearest interpolation of the event's array to the event's
+ * own length, then the default get_on_overlap cut with its one-sample replicate pad), 2 = chunk (the wav2vec cut of the
+ * overlap, then nearest interpolation to the overlap's length).  feat_default (HOST): the value of unpainted samples.
+ * mask_kind: -1 = the mask is all true, else true exactly where an event of that kind paints.
+ * kinds: [R][NK] entries (bm_features_table_entry_bytes(0) bytes each, filled by bm_features_kind_fill): the events of
+ * one kind of one recording in painting order -- start (non-decreasing), duration and the running maximum of start +
+ * duration, float64 on the device; within a kind a later event overwrites an earlier one.  srcs: [R][NF] entries
+ * (..entry_bytes(1), bm_features_source_fill): constant = float [n][channels] on the device; otherwise n entries
+ * (..entry_bytes(2), bm_features_array_fill) {address of the event's [channels][L] array, read in place, 1 <= L < 2^31,
+ * er = L / duration}.  rec: int32 [n_index], wstart / wdur: float64 [n_index] (the window's start and duration in
+ * seconds, from the host's division), the arrays of a whole epoch; a batch is the B segments from `first` on.
+ * A rec outside [0, R) is checked BEFORE any table address is formed: the segment is defaults (mask false, or true when
+ * mask_kind = -1) and *flag is set to 1 by a plain store.  T <= 4096 and NF <= 32, else BM_ERR_UNSUPPORTED; B <= 65535.
+ * No atomics, no scratch; B == 0 returns without a launch. */
+long bm_features_table_entry_bytes(int which);
+int bm_features_kind_fill(void* entry, const double* start, const double* dur, const double* runmax, long n);
+int bm_features_source_fill(void* entry, const void* data);
+int bm_features_array_fill(void* entry, const float* base, long L, double er);
+int bm_segment_features(const int* feat_table, const float* feat_default, int NF, int NK, int mask_kind,
+                        const void* kinds, const void* srcs, int R, const int* rec, const double* wstart,
+                        const double* wdur, long n_index, long first, int B, int F, int T, double sr, float* dst,
+                        unsigned char* mask, int* flag, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
