@@ -1767,3 +1767,187 @@ def segment_features(table: EventTable, rec: torch.Tensor, wstart: torch.Tensor,
                                         _p(dest_mask), _p(flag), _stream()), "bm_segment_features")
     _timed("segment_features", 0., launch)
     return dest, dest_mask
+
+
+# ------------------------------------------------------------------------------------------------
+# The MelSpectrum targets from resident waveforms (csrc/mel.hip, bm/features/audio.py:31-76).  torchaudio is not part
+# of this stack: its MelSpectrogram is restated from its documentation (torch.stft with center=True, reflect padding and
+# a periodic Hann window of n_fft samples; "normalized" divides by sqrt(sum w^2); |.|^2; the htk filterbank of
+# melscale_fbanks with norm=None, f_min = 0, f_max = in_sampling // 2).
+MEL_FRAME_TILE = 32            # frames per workgroup for n_fft <= 1024 (``mel_frame_tile``: 16 beyond)
+MEL_MIN_NFFT, MEL_MAX_NFFT, MEL_MAX_MELS, MEL_MAX_WAVES = 8, 2048, 256, 65535
+_mel_host_cache: tp.Dict[tp.Any, tp.Any] = {}
+_mel_device_cache: tp.Dict[tp.Any, tp.Any] = {}
+
+
+def mel_frame_tile(n_fft: int) -> int:
+    """Frames that one workgroup of ``bm_mel_spectrogram`` owns."""
+    return int(lib().bm_mel_frame_tile(int(n_fft)))
+
+
+def mel_check_limits(n_fft: int, n_mels: int) -> None:
+    if not (isinstance(n_fft, int) and MEL_MIN_NFFT <= n_fft <= MEL_MAX_NFFT):
+        raise ValueError(f"mel spectrogram: n_fft = {n_fft}; the kernel takes {MEL_MIN_NFFT} <= n_fft <= {MEL_MAX_NFFT}")
+    if n_fft % 4:
+        raise ValueError(f"mel spectrogram: n_fft = {n_fft} is not a multiple of 4 (hop_length = n_fft // 4)")
+    if not (isinstance(n_mels, int) and 1 <= n_mels <= MEL_MAX_MELS):
+        raise ValueError(f"mel spectrogram: n_mels = {n_mels}; the kernel takes 1 <= n_mels <= {MEL_MAX_MELS}")
+
+
+def mel_filterbank(n_fft: int, n_mels: int, in_sampling: int):
+    """``(fb, lo, hi)``: ``melscale_fbanks(n_fft // 2 + 1, 0, in_sampling // 2, n_mels, in_sampling, norm=None,
+    mel_scale="htk")`` evaluated in fp64 and rounded once -- ``fb`` [n_fft // 2 + 1, n_mels] fp32 (CPU) -- and the bins
+    ``[lo[m], hi[m])`` that hold every non-zero weight of filter ``m`` (int32; ``lo == hi``: an all-zero filter, the
+    case torchaudio warns about).  Cached."""
+    key = ("fb", int(n_fft), int(n_mels), int(in_sampling))
+    hit = _mel_host_cache.get(key)
+    if hit is None:
+        mel_check_limits(n_fft, n_mels)
+        if int(in_sampling) < 2:
+            raise ValueError(f"mel spectrogram: in_sampling = {in_sampling}")
+        n_freqs = n_fft // 2 + 1
+        f_max = float(int(in_sampling) // 2)
+        all_freqs = np.linspace(0., f_max, n_freqs)
+        m_pts = np.linspace(0., 2595. * np.log10(1. + f_max / 700.), n_mels + 2)
+        f_pts = 700. * (10. ** (m_pts / 2595.) - 1.)
+        f_diff = f_pts[1:] - f_pts[:-1]
+        slopes = f_pts[None, :] - all_freqs[:, None]
+        fb64 = np.maximum(0., np.minimum(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]))
+        fb = fb64.astype(np.float32)
+        lo, hi = np.zeros(n_mels, np.int32), np.zeros(n_mels, np.int32)
+        for m in range(n_mels):
+            nz = np.flatnonzero(fb[:, m])
+            if len(nz):
+                lo[m], hi[m] = nz[0], nz[-1] + 1
+        hit = _mel_host_cache[key] = (torch.from_numpy(fb), torch.from_numpy(lo), torch.from_numpy(hi))
+    return hit
+
+
+def mel_basis(n_fft: int, normalized: bool) -> torch.Tensor:
+    """The DFT basis of the kernel, ``[n_fft, 2 * (n_fft // 2 + 1)]`` fp32 (CPU): column ``b`` is ``w[k] cos(2 pi k b /
+    n_fft) / norm``, column ``n_fft // 2 + 1 + b`` is ``-w[k] sin(2 pi k b / n_fft) / norm`` -- ``w`` the periodic Hann
+    window, ``norm = sqrt(sum w^2)`` when ``normalized`` else 1 -- evaluated in fp64, rounded once.  Cached."""
+    key = ("basis", int(n_fft), bool(normalized))
+    hit = _mel_host_cache.get(key)
+    if hit is None:
+        mel_check_limits(n_fft, 1)
+        k = np.arange(n_fft, dtype=np.int64)
+        w = 0.5 - 0.5 * np.cos(2. * np.pi * k / n_fft)
+        norm = np.sqrt(np.sum(w * w)) if normalized else 1.
+        angle = 2. * np.pi * ((k[:, None] * np.arange(n_fft // 2 + 1, dtype=np.int64)[None, :]) % n_fft) / n_fft
+        basis = np.concatenate([w[:, None] * np.cos(angle), -w[:, None] * np.sin(angle)], axis=1) / norm
+        hit = _mel_host_cache[key] = torch.from_numpy(basis.astype(np.float32))
+    return hit
+
+
+def _mel_device_tables(n_fft, n_mels, in_sampling, normalized, device):
+    """(basis [n_fft, 2 nbp] with the bins padded to a multiple of 16, nbp, fbw [n_mels, n_freqs], range [n_mels, 2] on
+    the device, the same range on the host), cached per device."""
+    n_freqs = n_fft // 2 + 1
+    nbp = (n_freqs + 15) // 16 * 16
+    kb = ("basis", n_fft, bool(normalized), device)
+    basis = _mel_device_cache.get(kb)
+    if basis is None:
+        host = mel_basis(n_fft, normalized)
+        padded = torch.zeros(n_fft, 2, nbp, dtype=torch.float32)
+        padded[:, 0, :n_freqs], padded[:, 1, :n_freqs] = host[:, :n_freqs], host[:, n_freqs:]
+        basis = _mel_device_cache[kb] = padded.reshape(n_fft, 2 * nbp).to(device)
+    kf = ("fb", n_fft, n_mels, int(in_sampling), device)
+    fb = _mel_device_cache.get(kf)
+    if fb is None:
+        w, lo, hi = mel_filterbank(n_fft, n_mels, in_sampling)
+        rng = torch.stack([lo, hi], dim=1).contiguous()
+        fb = _mel_device_cache[kf] = (w.t().contiguous().to(device), rng.to(device), rng.numpy())
+    return (basis, nbp) + fb
+
+
+def _wave_list(waves, what, min_len=0):
+    waves = list(waves)
+    if len(waves) > MEL_MAX_WAVES:
+        raise ValueError(f"{what}: {len(waves)} waveforms in one call, the limit is {MEL_MAX_WAVES}")
+    for i, x in enumerate(waves):                               # the limits first: they do not need a device
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and not 1 <= x.numel() < 2 ** 31:
+            raise ValueError(f"{what}: waveform {i} has {x.numel()} samples; the kernels take 1 <= L < 2^31")
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() <= min_len:
+            raise ValueError(f"{what}: waveform {i} has {x.numel()} samples; the reflect padding needs "
+                             f"L > n_fft // 2 = {min_len}")
+    for i, x in enumerate(waves):
+        _req(x, f"{what}: waveform {i}")
+        if x.dim() != 1 or x.device != waves[0].device:
+            raise BmHipError(f"{what}: waveform {i} of shape {tuple(x.shape)} on {x.device}; expected 1-D waveforms on one "
+                             "device")
+    return waves
+
+
+def _wave_table(waves, outs):
+    """The device table of csrc/mel.hip (a host buffer and ONE copy: no launch) and the lengths on the host."""
+    L = lib()
+    host = torch.zeros(len(waves), L.bm_mel_table_entry_bytes(), dtype=torch.uint8)
+    for i, x in enumerate(waves):
+        check(L.bm_mel_table_fill(ctypes.c_void_p(host[i].data_ptr()), _p(x), x.numel(), _p(outs[i]) if outs else None),
+              "bm_mel_table_fill")
+    return host.to(waves[0].device), np.ascontiguousarray([x.numel() for x in waves], dtype=np.int64)
+
+
+def _wave_tickets(n: int, device) -> torch.Tensor:
+    """``n`` zeroed ticket counters of this stream (every launch leaves them at zero again, csrc/bm_block.h)."""
+    key = ("tickets", device, torch.cuda.current_stream(device).cuda_stream)
+    t = _mel_device_cache.get(key)
+    if t is None or t.numel() < n:
+        t = _mel_device_cache[key] = torch.zeros(max(n, 1024), dtype=torch.int32, device=device)
+    return t
+
+
+def _wave_moments(table, lengths, device) -> torch.Tensor:
+    n = len(lengths)
+    max_splits = max(int(lib().bm_wave_moments_splits(int(v))) for v in lengths)
+    tickets = _wave_tickets(n, device)
+    part = torch.empty(n, max_splits, 2, dtype=torch.float64, device=device)
+    mom = torch.empty(n, 2, dtype=torch.float64, device=device)
+
+    def launch():
+        check(lib().bm_wave_moments(_p(table), ctypes.c_void_p(lengths.ctypes.data), n, _p(tickets), _p(part), max_splits,
+                                    _p(mom), _stream()), "bm_wave_moments")
+    _timed("wave_moments", 0., launch)
+    return mom
+
+
+def wave_moments(waves: tp.Sequence[torch.Tensor]) -> torch.Tensor:
+    """``[n, 2]`` float64 on the device: ``(mean, 1 / (1e-8 + unbiased std))`` of every 1-D fp32 device waveform, in fp64,
+    ONE launch for all of them and no host read-back -- the ``(shift, scale)`` of MelSpectrum's ``norm_audio``."""
+    waves = _wave_list(waves, "wave_moments")
+    if not waves:
+        raise BmHipError("wave_moments: no waveform")
+    table, lengths = _wave_table(waves, None)
+    return _wave_moments(table, lengths, waves[0].device)
+
+
+def mel_spectrograms(waves: tp.Sequence[torch.Tensor], n_mels: int = 40, n_fft: int = 512, in_sampling: int = 16_000,
+                     normalized: bool = True, use_log_scale: bool = True, log_scale_eps: float = 1e-5,
+                     norm_audio: bool = True) -> tp.List[torch.Tensor]:
+    """What ``MelSpectrum._compute`` (bm/features/audio.py:61-76) returns for every mono waveform at ``in_sampling``:
+    a list of ``[n_mels, 1 + L // (n_fft // 4)]`` fp32 tensors, carved from one allocation.  ``waves``: 1-D fp32 device
+    tensors, read in place (4-byte alignment is all that is assumed).  Two launches for the whole list (one with
+    ``norm_audio=False``): the statistics, then framing, reflect padding, window, DFT, power, filterbank and log."""
+    mel_check_limits(n_fft, n_mels)
+    waves = _wave_list(waves, "mel_spectrograms", n_fft // 2)
+    if not waves:
+        return []
+    hop = n_fft // 4
+    device = waves[0].device
+    basis, nbp, fbw, rng, rng_host = _mel_device_tables(n_fft, n_mels, in_sampling, normalized, device)
+    frames = [1 + x.numel() // hop for x in waves]
+    flat = torch.empty(n_mels * sum(frames), dtype=torch.float32, device=device)
+    outs, at = [], 0
+    for f in frames:
+        outs.append(flat[at:at + n_mels * f].view(n_mels, f))
+        at += n_mels * f
+    table, lengths = _wave_table(waves, outs)
+    mom = _wave_moments(table, lengths, device) if norm_audio else None
+
+    def launch():
+        check(lib().bm_mel_spectrogram(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), _p(mom), _p(basis),
+                                       n_fft, nbp, _p(fbw), _p(rng), ctypes.c_void_p(rng_host.ctypes.data), n_mels,
+                                       int(bool(use_log_scale)), float(log_scale_eps), _stream()), "bm_mel_spectrogram")
+    _timed("mel_spectrogram", 4. * n_fft * nbp * sum(frames), launch)
+    return outs

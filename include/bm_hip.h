@@ -472,6 +472,38 @@ int bm_segment_features(const int* feat_table, const float* feat_default, int NF
                         const double* wdur, long n_index, long first, int B, int F, int T, double sr, float* dst,
                         unsigned char* mask, int* flag, void* stream);
 
+/* ---- the MelSpectrum targets from resident waveforms (mel.hip)  bm/features/audio.py:61-76 ----
+ * MelSpectrum._compute behind the channel mean: (wav - wav.mean()) / (1e-8 + wav.std()) (unbiased std), then
+ * torchaudio.transforms.MelSpectrogram(n_fft, hop = n_fft / 4, normalized) RESTATED from its documentation -- torch.stft
+ * with center=True, reflect padding, a periodic Hann window of n_fft samples, divided by sqrt(sum w^2) when normalized,
+ * |.|^2, times the htk filterbank -- and log10(mel + eps).  Two launches for any number of waveforms.
+ * table: n_waves entries (bm_mel_table_entry_bytes bytes each, filled on the host by bm_mel_table_fill) {address of a 1-D
+ * fp32 waveform on the device, read in place, 4-byte aligned; its length, 1 <= L < 2^31; address of its [n_mels][1 + L /
+ * hop] output (null for bm_wave_moments)}.  lengths (HOST memory): the same lengths, for the grid and the checks.
+ * bm_wave_moments: mom[w] = {mean, 1 / (1e-8 + unbiased std)} in fp64, ONE launch over a (split, waveform) grid: a
+ * waveform is cut into bm_wave_moments_splits(L) splits (a function of L alone), every split is walked twice (its sum,
+ * then its squares centred on its own mean) and the workgroup of a waveform that finishes last folds the partials in
+ * split order.  tickets: n_waves counters, ZEROED by the caller once (every launch leaves them at zero); part: room for
+ * [n_waves][max_splits][2] doubles.  L = 1 gives a NaN scale, like torch.std.
+ * bm_mel_spectrogram: ONE launch over a (frame tile of bm_mel_frame_tile(n_fft) frames, waveform) grid; every output
+ * element is stored exactly once, no atomics.  mom: what bm_wave_moments wrote, or null for (0, 1); a sample enters as
+ * (float)(((double)x - shift) * scale).  basis: [n_fft][2 nbp] fp32, nbp = n_fft / 2 + 1 rounded up to 16: column b <
+ * nbp is w[k] cos(2 pi k b / n_fft) / norm, column nbp + b is -w[k] sin(...) / norm, zero for b > n_fft / 2.  The
+ * contraction is v_mfma_f32_16x16x4_f32 in one fixed blocked order (per quarter of the window: chains of 8 samples with
+ * k ascending, added in ascending order; quarters folded as (q0 + q1) + (q2 + q3)): a frame's bits do not depend on its
+ * tile, the grid or the other waveforms.  fbw: [n_mels][n_fft / 2 + 1] filter weights; range (device) and range_host (HOST, the same values):
+ * [n_mels][2] = the bins [lo, hi) that row m sums, ascending, by fmaf from 0.f.  8 <= n_fft <= 2048, n_fft % 4 == 0,
+ * n_mels <= 256, n_fft / 2 < L, n_waves <= 65535. */
+long bm_mel_table_entry_bytes(void);
+int bm_mel_table_fill(void* entry, const float* x, long L, float* out);
+int bm_mel_frame_tile(int n_fft);
+int bm_wave_moments_splits(long L);
+int bm_wave_moments(const void* table, const long* lengths, int n_waves, unsigned* tickets, double* part,
+                    int max_splits, double* mom, void* stream);
+int bm_mel_spectrogram(const void* table, const long* lengths, int n_waves, const double* mom, const float* basis,
+                       int n_fft, int nbp, const float* fbw, const int* range, const int* range_host, int n_mels,
+                       int use_log, float eps, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
