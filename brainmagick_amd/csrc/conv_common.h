@@ -172,3 +172,21 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvNNArgs& a, f32x16 (
         }
     }
 }
+
+// host: the contract that the NN conv entry points share, checked and filled into `a` (`family` names the entry point
+// in the messages).  Left to the family: its kernel-size rule, Mpad, nchunk and the tile counts.
+static inline int conv_nn_fill_args(ConvNNArgs& a, const char* family, const float* x, long x_bstride, const float* wp,
+                                    const int* widx, const float* bias, long bias_gstride, const float* ep_scale,
+                                    const float* ep_shift, const float* res, long res_bstride, float* y_pre,
+                                    float* y_out, long y_bstride, float* stats, int B, int Cin, int M, int T, int KS,
+                                    int dil, int act, float leak) {
+    BM_REQUIRE(x && wp, "%s: null x/w", family);
+    BM_REQUIRE(y_pre || y_out, "%s: no output", family);
+    BM_REQUIRE(B >= 0 && Cin > 0 && M > 0 && T > 0 && dil >= 1, "%s: bad dims", family);
+    BM_REQUIRE((ep_scale == nullptr) == (ep_shift == nullptr), "%s: scale/shift must come together", family);
+    a.x = x; a.x_bstride = x_bstride; a.wp = wp; a.widx = widx; a.bias = bias; a.bias_gstride = bias_gstride;
+    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.res = res; a.res_bstride = res_bstride;
+    a.y_pre = y_pre; a.y_out = y_out; a.y_bstride = y_bstride; a.stats = stats;
+    a.B = B; a.Cin = Cin; a.M = M; a.T = T; a.KS = KS; a.dil = dil; a.act = act; a.leak = leak;
+    return BM_OK;
+}

@@ -1,5 +1,5 @@
-// Shared by the two wide f16x2 conv translation units (conv_nn_h2w.hip: the production main loop, conv_nn_h2d.hip: the
-// round-2..5 main loop kept for A/B runs): argument block, operand split, tile epilogue (the scale rule: mfma_split.h).
+// Shared by the wide f16x2 conv (conv_nn_h2w.hip) and the weight packing / amax scan that feed it (pack_h2.hip):
+// argument block, tile constants, tile epilogue (the scale rule: mfma_split.h).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -7,11 +7,11 @@
 #include "mfma_split.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4h __attribute__((ext_vector_type(4)));
 
 #define HBN 192           // columns of the workgroup tile (2 wavefront columns x 3 blocks)
 #define HXWP 256          // padded x-window width (>= 192 + 2 * 16; one column per thread)
 #define HXSLAB (2 * 2 * HXWP)     // 16-byte slots of one X buffer
+#define PACK_MAX_NK 3840  // Cin * KS values of one weight row that the packing kernel's LDS tile holds (61 KB)
 
 struct ConvH2Args {
     ConvNNArgs c;
@@ -19,26 +19,6 @@ struct ConvH2Args {
     const float* wscale;      // [G][Mpad] inverse row scales written by bm_pack_weights_h2
     BmAmaxDst y_amax;         // where max |y_out| goes (bm_publish_amax): per-workgroup partials
 };
-
-// 8 fp32 values (already scaled) -> f16 planes hi, lo
-__device__ __forceinline__ void split8h(const float* f, float s, u32x4& hi, u32x4& lo) {
-    f16x8 h, l;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float xs = f[i] * s;
-        const _Float16 a = (_Float16)xs;
-        h[i] = a;
-        l[i] = (_Float16)(xs - (float)a);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
-__device__ __forceinline__ float ch_ld32(i32x4h rs, int voff) {
-    float v;
-    asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(rs) : "memory");
-    return v;
-}
 
 // Epilogue helpers: every accumulator block is addressed with compile-time indices (template recursion), so
 // the MW x 3 accumulators never leave the register file.
@@ -225,7 +205,7 @@ __device__ __forceinline__ void h2_tile_stats(const ConvNNArgs& a, f32x16 (&acc)
     });
 }
 
-// Epilogue of a tile, shared by the two main loops below: inverse scales (exact powers of two), bias, optional
+// Epilogue of a tile: inverse scales (exact powers of two), bias, optional
 // pre-activation store, per-channel affine, activation, residual, BatchNorm partial sums, max |y|.  One literal-indexed
 // expansion per accumulator block keeps the accumulators in registers.  `smem` is the workgroup's LDS, free by now
 // (the caller's last barrier): ep[0 .. 3 HBM) = staged row parameters, ep[3 HBM .. 4 HBM) = per-row accumulator
@@ -354,5 +334,6 @@ __device__ __forceinline__ void h2_tile_epilogue(const ConvH2Args& args, f32x16 
 #define CH_T(I_)
 #endif
 
-// conv_nn_h2d.hip: launch of the LDS-DMA-staged main loop (BM_CONV_LDSDMA=1)
-int bm_launch_conv_nn_h2d(const ConvH2Args& args, int KS, int mw, size_t lds_bytes, unsigned nblocks, hipStream_t stream);
+// host entry points that one of the two translation units defines and the other calls
+extern "C" int bm_conv_h2_mpad(int M);                                                     // conv_nn_h2w.hip
+extern "C" int bm_amax(const float* x, long n, float* out, float* ws, void* stream);      // pack_h2.hip

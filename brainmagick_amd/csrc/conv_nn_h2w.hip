@@ -7,7 +7,7 @@
 // products  a.lo * b.hi + a.hi * b.lo + a.hi * b.hi  (the dropped a.lo * b.lo is <= 2^-22 |a b|), each an
 // EXACT f16 x f16 product accumulated in fp32 by v_mfma_f32_32x32x16_f16; the accumulator is multiplied by
 // the (exact) inverse scales in the epilogue.  Three 16-bit MFMAs per fp32-accurate 32x32x16 block instead of
-// the six of the 3 x bf16 split (conv_nn_x3w.hip): half the matrix-core time for the same parity tolerances --
+// the six of the 3 x bf16 split (conv_nn_x3.hip): half the matrix-core time for the same parity tolerances --
 // measured rel-L2 against fp64 is that of an fp32 FMA chain (tests/test_exact_f32_gpu.py), because the fp32
 // accumulation error dominates both.  The error bound is norm-wise (relative to the largest element of the
 // tensor / weight row), not element-wise: an element 2^-18 below its tensor's maximum keeps fewer than 22
@@ -18,7 +18,7 @@
 // (16-channel chunk, tap) = 9 MW MFMAs per wavefront.  LDS: X [2 buffers][2 planes][2 groups][256 columns] x 16 B
 // (the weights do not pass through it, see below).
 // Packed weights: [g][chunk32][tap][plane][4 groups][Mpad] 16-byte slots (8 f16 channels), followed by the
-// per-row inverse scales [G][Mpad] fp32 (bm_pack_weights_h2).
+// per-row inverse scales [G][Mpad] fp32 (bm_pack_weights_h2, pack_h2.hip).
 #include "conv_h2_common.h"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -27,8 +27,8 @@
 // The packed layout [chunk32][tap][plane][4 groups][Mpad] x 16 B already is fragment order -- lane (nl, h) of row
 // block mt wants the slot (group = 2 (c16 & 1) + h, row = m0 + wm 32 MW + 32 mt + nl) -- so a wavefront fetches a
 // fragment with ONE buffer_load_dwordx4 (two 512-byte runs), one stage ahead, into a second register set: no LDS-DMA
-// copy, no LDS write, no ds_read for A (the stage of conv_nn_h2d_kernel below: 5 copies + 10 reads per wavefront, and
-// a workgroup barrier per STAGE because the slab is shared).  LDS holds only the two X window buffers, and the
+// copy, no LDS write, no ds_read for A (the stage of the LDS-DMA loop of rounds 2-5: 5 copies + 10 reads per wavefront, and
+// a workgroup barrier per STAGE because the slab was shared).  LDS holds only the two X window buffers, and the
 // workgroup meets at one barrier per 16-channel chunk.  B fragments are double-buffered too (read during the
 // previous stage), so a stage is 3 MW NW MFMAs on operands that are all in registers when it starts:
 //     term 0: A.lo x B.hi,  term 1: A.hi x B.lo,  term 2: A.hi x B.hi.
@@ -326,7 +326,7 @@ extern "C" int bm_conv_h2_covers(int Cin, int M, int T, int KS, int dil) {
     if (KS != 1 && KS != 3) return 0;
     if ((KS >> 1) * dil > 16 || T <= 128) return 0;
     if ((long)Cin * T * 4 >= 0x40000000L) return 0;
-    if ((long)Cin * KS > 3840) return 0;              // PACK_MAX_NK: a weight row must fit the packing kernel's LDS tile
+    if ((long)Cin * KS > PACK_MAX_NK) return 0;       // a weight row must fit the packing kernel's LDS tile
     // padded rows are wasted MFMA work: leave tiny layers (tests, F = 16 heads) to the narrow kernels
     return (long)bm_conv_h2_mpad(M) * 2 <= (long)M * 3 || M >= 96;
 }
@@ -334,241 +334,16 @@ extern "C" int bm_conv_h2_covers(int Cin, int M, int T, int KS, int dil) {
 // rows of the `stats` buffer of bm_conv1d_nn_h2: one per (segment, column tile, wavefront column)
 extern "C" int bm_conv_h2_stats_tiles(int B, int T) { return B * cdiv(T, HBN) * 2; }
 
-// bytes of the packed buffer: f16 planes [G][chunk32][KS][2][4][Mpad][8] + fp32 inverse row scales [G][Mpad]
-extern "C" long bm_packed_weight_bytes_h2(int G, int M, int Cin, int KS) {
-    const long mpad = bm_conv_h2_mpad(M);
-    return (long)G * cdiv(Cin, 32) * KS * 2 * 4 * mpad * 8 * 2 + (long)G * mpad * 4;
-}
-
-// One workgroup per (group, padded row): row maximum -> power-of-two scale -> the row's 16-byte slots of both
-// planes (zeros for padded rows / channels) and its inverse scale.
-struct PackH2Job {
-    const float* src;
-    unsigned short* dst;
-    float* wscale;
-    const float* alpha;
-    long sg, sm, sc, sj;
-    int M, Cin, KS, flip, Mpad, nchunk;
-    int block0, nblocks;      // workgroups [block0, block0 + nblocks) of a batched launch belong to this job
-};
-
-// PACK_ROWS consecutive rows per workgroup of 256 threads (one wavefront per row), staged through LDS so that both
-// source layouts are read along their contiguous direction: the forward layout a whole row at a time, the
-// transposed (data-gradient) layout PACK_ROWS x KS contiguous floats per channel -- read element by element it
-// touched a different cache line with every value and the 36 MB of parameters took 175 us to pack.
-#define PACK_ROWS 4
-#define PACK_MAX_NK 3840      // Cin * KS values of one row that the LDS tile holds (61 KB)
-
-__device__ __forceinline__ void pack_h2_rows(const PackH2Job& jb, int block, float* tile, float* rs) {
-    const float* __restrict__ src = jb.src;
-    const int M = jb.M, Cin = jb.Cin, KS = jb.KS, Mpad = jb.Mpad, nchunk = jb.nchunk, flip = jb.flip;
-    const long sg = jb.sg, sm = jb.sm, sc = jb.sc, sj = jb.sj;
-    const int rows_per_group = Mpad / PACK_ROWS;
-    const int g = block / rows_per_group, m0 = (block - g * rows_per_group) * PACK_ROWS;
-    const float alpha = jb.alpha ? *jb.alpha : 1.f;
-    const int nk = Cin * KS;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // 1. tile[r][c * KS + j] = alpha * w[m0 + r][c][j]; the faster of (row, channel) in memory runs inside
-    const float* base = src + g * sg + (long)m0 * sm;
-    const bool rows_inside = sm < sc;
-    for (int idx = tid; idx < PACK_ROWS * nk; idx += blockDim.x) {
-        int r, c, j;
-        if (rows_inside) {                  // idx = (c * PACK_ROWS + r) * KS + j
-            j = idx % KS;
-            const int t = idx / KS;
-            r = t % PACK_ROWS;
-            c = t / PACK_ROWS;
-        } else {                            // idx = (r * Cin + c) * KS + j
-            j = idx % KS;
-            const int t = idx / KS;
-            c = t % Cin;
-            r = t / Cin;
-        }
-        tile[r * nk + c * KS + j] = (m0 + r < M) ? alpha * base[r * sm + c * sc + j * sj] : 0.f;
-    }
-    __syncthreads();
-    // 2. row maxima -> scales (wavefront w owns row w)
-    {
-        float mx = 0.f;
-        for (int i = lane; i < nk; i += 64) mx = fmaxf(mx, fabsf(tile[wave * nk + i]));
-        mx = bm_wave_max(mx);
-        float s, inv;
-        bm_scale_from_amax(mx, s, inv);
-        if (lane == 0) {
-            rs[wave] = s;
-            jb.wscale[(long)g * Mpad + m0 + wave] = inv;
-        }
-    }
-    __syncthreads();
-    // 3. the rows' 16-byte slots of both planes: slot q = (chunk, tap, 8-channel group); rows run fastest so that
-    //    neighbouring threads write neighbouring 16-byte slots
-    const int nslots = nchunk * KS * 4;
-    const long plane_stride = (long)4 * Mpad * 8;           // f16 elements of one plane of one (chunk, tap)
-    for (int t = tid; t < PACK_ROWS * nslots; t += blockDim.x) {
-        const int r = t % PACK_ROWS, q = t / PACK_ROWS;
-        const int kg = q & 3;
-        const int j = (q >> 2) % KS;
-        const int chunk = (q >> 2) / KS;
-        const int jj = flip ? KS - 1 - j : j;
-        const float sr = rs[r];
-        alignas(16) unsigned short hi[8];
-        alignas(16) unsigned short lo[8];
-#pragma unroll
-        for (int e8 = 0; e8 < 8; ++e8) {
-            const int c = chunk * 32 + kg * 8 + e8;
-            const float v = c < Cin ? tile[r * nk + c * KS + jj] * sr : 0.f;
-            const _Float16 a = (_Float16)v;
-            const _Float16 l = (_Float16)(v - (float)a);
-            hi[e8] = __builtin_bit_cast(unsigned short, a);
-            lo[e8] = __builtin_bit_cast(unsigned short, l);
-        }
-        const long stage = ((long)g * nchunk + chunk) * KS + j;
-        unsigned short* out = jb.dst + stage * 2 * plane_stride + ((long)kg * Mpad + m0 + r) * 8;
-        *reinterpret_cast<uint4*>(out) = *reinterpret_cast<const uint4*>(hi);
-        *reinterpret_cast<uint4*>(out + plane_stride) = *reinterpret_cast<const uint4*>(lo);
-    }
-}
-
-__global__ __launch_bounds__(256) void pack_weights_h2_kernel(PackH2Job jb) {
-    extern __shared__ float pack_smem[];
-    pack_h2_rows(jb, blockIdx.x, pack_smem + PACK_ROWS, pack_smem);
-}
-
-// every weight tensor of a model in ONE launch: `jobs` (device memory) sorted by block0
-__global__ __launch_bounds__(256) void pack_weights_h2_batch_kernel(const PackH2Job* __restrict__ jobs, int njobs) {
-    extern __shared__ float pack_smem[];
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {                                   // last job with block0 <= blockIdx.x
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const PackH2Job jb = jobs[lo];
-    pack_h2_rows(jb, blockIdx.x - jb.block0, pack_smem + PACK_ROWS, pack_smem);
-}
-
-static int pack_h2_fill(PackH2Job& jb, const float* src, void* dst, int G, int M, int Cin, int KS, long sg, long sm,
-                        long sc, long sj, int flip, const float* alpha_ptr) {
-    BM_REQUIRE(src && dst, "pack_weights_h2: null pointer");
-    BM_REQUIRE(G > 0 && M > 0 && Cin > 0 && KS > 0, "pack_weights_h2: bad dims");
-    jb.Mpad = bm_conv_h2_mpad(M);
-    jb.nchunk = cdiv(Cin, 32);
-    const long f16_elems = (long)G * jb.nchunk * KS * 2 * 4 * jb.Mpad * 8;
-    jb.src = src; jb.dst = (unsigned short*)dst;
-    jb.wscale = reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + f16_elems * 2);
-    jb.alpha = alpha_ptr;
-    jb.sg = sg; jb.sm = sm; jb.sc = sc; jb.sj = sj;
-    jb.M = M; jb.Cin = Cin; jb.KS = KS; jb.flip = flip;
-    BM_REQUIRE(Cin * KS <= PACK_MAX_NK, "pack_weights_h2: Cin * KS = %d exceeds %d", Cin * KS, PACK_MAX_NK);
-    jb.block0 = 0; jb.nblocks = G * jb.Mpad / PACK_ROWS;
-    return BM_OK;
-}
-
-extern "C" int bm_pack_weights_h2(const float* src, void* dst, int G, int M, int Cin, int KS, long sg, long sm,
-                                  long sc, long sj, int flip, const float* alpha_ptr, void* stream) {
-    PackH2Job jb;
-    if (int rc = pack_h2_fill(jb, src, dst, G, M, Cin, KS, sg, sm, sc, sj, flip, alpha_ptr)) return rc;
-    hipLaunchKernelGGL(pack_weights_h2_kernel, dim3((unsigned)jb.nblocks), dim3(256),
-                       (size_t)(PACK_ROWS + PACK_ROWS * Cin * KS) * sizeof(float), (hipStream_t)stream, jb);
-    return bm_check_launch("pack_weights_h2");
-}
-
-// Batched packing.  The host builds a table of jobs (bm_pack_h2_job_bytes() bytes each, filled by
-// bm_pack_h2_job_fill, which returns the job's workgroup count or a negative error), copies it to the device
-// once, and re-packs every weight tensor of the model with one launch per optimizer step.
-extern "C" int bm_pack_h2_job_bytes() { return (int)sizeof(PackH2Job); }
-
-extern "C" int bm_pack_h2_job_fill(void* job, const float* src, void* dst, int G, int M, int Cin, int KS, long sg,
-                                   long sm, long sc, long sj, int flip, const float* alpha_ptr, int block0) {
-    if (!job) return -1;
-    PackH2Job jb;
-    if (pack_h2_fill(jb, src, dst, G, M, Cin, KS, sg, sm, sc, sj, flip, alpha_ptr)) return -1;
-    jb.block0 = block0;
-    memcpy(job, &jb, sizeof(jb));
-    return jb.nblocks;
-}
-
-extern "C" int bm_pack_weights_h2_batch(const void* jobs_dev, int njobs, int total_blocks, int max_nk, void* stream) {
-    BM_REQUIRE(jobs_dev && njobs > 0 && total_blocks > 0, "pack_weights_h2_batch: bad arguments");
-    BM_REQUIRE(max_nk > 0 && max_nk <= PACK_MAX_NK, "pack_weights_h2_batch: max_nk = %d (largest Cin * KS of the jobs)", max_nk);
-    hipLaunchKernelGGL(pack_weights_h2_batch_kernel, dim3((unsigned)total_blocks), dim3(256),
-                       (size_t)(PACK_ROWS + PACK_ROWS * max_nk) * sizeof(float), (hipStream_t)stream,
-                       (const PackH2Job*)jobs_dev, njobs);
-    return bm_check_launch("pack_weights_h2_batch");
-}
-
-// max |x[i]| as <= 256 per-workgroup partial maxima (ws) folded by bm_amax_finalize into the slot `out`
-// (BM_AMAX_SHARDS floats whose maximum is the answer).  A non-finite input yields a non-finite or NaN-free
-// maximum of the finite part; the non-finite values themselves propagate through the consumer's split.
-__global__ __launch_bounds__(1024) void amax_kernel(const float* __restrict__ x, long n, float* __restrict__ ws,
-                                                    int* __restrict__ nonfinite) {
-    __shared__ float sh[16];
-    float mx = 0.f;
-    unsigned top = 0u;                                  // largest |x| bit pattern: >= 0x7f800000 <=> inf / nan seen
-    // a tensor that is only 4-byte aligned (a batch slice such as meg[1:] with C * T odd): `head` scalar elements
-    // up to the first 16-byte boundary, the vector body from there, the scalar tail behind it
-    long head = (long)((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2;
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    const float4* x4 = reinterpret_cast<const float4*>(x + head);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const float4 v = x4[i];
-        mx = fmaxf(fmaxf(mx, fabsf(v.x)), fmaxf(fabsf(v.y), fmaxf(fabsf(v.z), fabsf(v.w))));
-        top = max(max(top, __float_as_uint(v.x) & 0x7fffffffu),
-                  max(__float_as_uint(v.y) & 0x7fffffffu, max(__float_as_uint(v.z) & 0x7fffffffu,
-                                                               __float_as_uint(v.w) & 0x7fffffffu)));
-    }
-    if (blockIdx.x == 0) {
-        const long tail0 = head + (n4 << 2);
-        for (long i = threadIdx.x; i < head + (n - tail0); i += blockDim.x) {
-            const long k = i < head ? i : tail0 + (i - head);
-            mx = fmaxf(mx, fabsf(x[k]));
-            top = max(top, __float_as_uint(x[k]) & 0x7fffffffu);
-        }
-    }
-    if (nonfinite && top >= 0x7f800000u) atomicOr(nonfinite, 1);     // rare: at most one atomic per thread
-    bm_publish_amax(mx, ws, sh);
-}
-
-// `nonfinite_flag` (nullable, device int): set to 1 if x holds an inf or a nan -- the reference's
-// `torch.isfinite(x).all()` asserts (bm/solver.py:258-260) ride on the pass that the f16x2 scale needs anyway.
-extern "C" int bm_amax_checked(const float* x, long n, float* out, float* ws, int* nonfinite_flag, void* stream) {
-    BM_REQUIRE(x && out && ws && n >= 0, "amax: bad arguments");
-    BM_REQUIRE(((uintptr_t)x & 3) == 0, "amax: x must be 4-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    long blocks = (n / 4 + 1023) / 1024;
-    blocks = blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);
-    hipLaunchKernelGGL(amax_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, x, n, ws, nonfinite_flag);
-    if (int rc = bm_check_launch("amax")) return rc;
-    return bm_amax_finalize(ws, (int)blocks, out, s);
-}
-
-extern "C" int bm_amax(const float* x, long n, float* out, float* ws, void* stream) {
-    return bm_amax_checked(x, n, out, ws, nullptr, stream);
-}
-
 template <int KS, int MW>
 static int launch_conv_nn_h2w(ConvH2Args args, float* y_amax_out, hipStream_t stream) {
     constexpr int HBM = 64 * MW;
-    size_t lds = (size_t)(3 * 2 * 2 * HBM + 2 * HXSLAB) * 16;
+    // the two X window buffers, 2 HXSLAB x 16 B = 32 KB: under the 64 KB above which a launch needs the opt-in attribute
     const size_t lds_ep = (size_t)(4 * HBM + 4) * sizeof(float);
-    if (lds < lds_ep) lds = lds_ep;
-    // BM_CONV_LDSDMA=1: the round-2..5 main loop (weight slabs by LDS-DMA, a barrier per stage; conv_nn_h2d.hip), for A/B runs
-    static const bool ldsdma = [] { const char* e = getenv("BM_CONV_LDSDMA"); return e && e[0] == '1'; }();
-    if (!ldsdma) lds = (size_t)(2 * HXSLAB) * 16 > lds_ep ? (size_t)(2 * HXSLAB) * 16 : lds_ep;
+    const size_t lds = (size_t)(2 * HXSLAB) * 16 > lds_ep ? (size_t)(2 * HXSLAB) * 16 : lds_ep;
     // y_out = conv + bias + residual and nothing else (the data-gradient convs of the residual layers, all 3-tap): the
     // kernel with the two-phase residual epilogue
     const ConvNNArgs& c = args.c;
-    const bool resk = KS == 3 && !ldsdma && c.res && c.y_out && !c.y_pre && !c.ep_scale && !c.stats && c.act == BM_ACT_NONE;
-    static bool attr_set = false;
-    if (!ldsdma && !attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_nn_h2w_kernel<KS, MW, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess && KS == 3)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_nn_h2w_kernel<KS, MW, KS == 3>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return bm_set_error((int)e, "conv_nn_h2w: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    const bool resk = KS == 3 && c.res && c.y_out && !c.y_pre && !c.ep_scale && !c.stats && c.act == BM_ACT_NONE;
     args.c.ntiles_n = cdiv(args.c.T, HBN);
     args.c.ntiles_m = args.c.Mpad / HBM;
     const long nblocks = (long)args.c.B * args.c.ntiles_n * args.c.ntiles_m;
@@ -577,9 +352,7 @@ static int launch_conv_nn_h2w(ConvH2Args args, float* y_amax_out, hipStream_t st
     const bool publish = y_amax_out && args.y_amax.ws && nblocks <= BM_AMAX_WS;
     float* ws = args.y_amax.ws;
     if (!publish) args.y_amax = BmAmaxDst{nullptr};
-    if (ldsdma) {
-        if (int rc = bm_launch_conv_nn_h2d(args, KS, MW, lds, (unsigned)nblocks, stream)) return rc;
-    } else if (resk)
+    if (resk)
         hipLaunchKernelGGL((conv_nn_h2w_kernel<KS, MW, KS == 3>), dim3((unsigned)nblocks), dim3(256), lds, stream, args);
     else
         hipLaunchKernelGGL((conv_nn_h2w_kernel<KS, MW, false>), dim3((unsigned)nblocks), dim3(256), lds, stream, args);
@@ -599,20 +372,18 @@ extern "C" int bm_conv1d_nn_h2(const float* x, long x_bstride, const float* x_am
                                const float* res, long res_bstride, float* y_pre, float* y_out, long y_bstride,
                                float* stats, int B, int Cin, int M, int T, int KS, int dil, int act, float leak,
                                int G, float* y_amax_out, float* amax_ws, void* stream) {
-    BM_REQUIRE(x && wpacked && x_amax, "conv1d_nn_h2: null x / w / x_amax");
-    BM_REQUIRE(y_pre || y_out, "conv1d_nn_h2: no output");
+    BM_REQUIRE(x_amax, "conv1d_nn_h2: null x_amax");
+    BM_REQUIRE(G >= 1, "conv1d_nn_h2: bad dims");
     BM_REQUIRE(!stats || (y_pre && !y_out && !ep_scale && act == BM_ACT_NONE && !res),
                "conv1d_nn_h2: per-tile statistics come with y_pre alone (the training-mode BatchNorm layers)");
-    BM_REQUIRE(B >= 0 && Cin > 0 && M > 0 && T > 0 && dil >= 1 && G >= 1, "conv1d_nn_h2: bad dims");
-    BM_REQUIRE((ep_scale == nullptr) == (ep_shift == nullptr), "conv1d_nn_h2: scale/shift must come together");
-    BM_REQUIRE(bm_conv_h2_covers(Cin, M, T, KS, dil), "conv1d_nn_h2: shape not covered (Cin=%d M=%d T=%d KS=%d dil=%d)",
-               Cin, M, T, KS, dil);
     ConvH2Args args;
     ConvNNArgs& a = args.c;
-    a.x = x; a.x_bstride = x_bstride; a.wp = (const float*)wpacked; a.widx = widx; a.bias = bias; a.bias_gstride = bias_gstride;
-    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.res = res; a.res_bstride = res_bstride;
-    a.y_pre = y_pre; a.y_out = y_out; a.y_bstride = y_bstride; a.stats = stats;
-    a.B = B; a.Cin = Cin; a.M = M; a.T = T; a.KS = KS; a.dil = dil; a.act = act; a.leak = leak;
+    if (int e = conv_nn_fill_args(a, "conv1d_nn_h2", x, x_bstride, (const float*)wpacked, widx, bias, bias_gstride, ep_scale,
+                                  ep_shift, res, res_bstride, y_pre, y_out, y_bstride, stats, B, Cin, M, T, KS, dil, act,
+                                  leak))
+        return e;
+    BM_REQUIRE(bm_conv_h2_covers(Cin, M, T, KS, dil), "conv1d_nn_h2: shape not covered (Cin=%d M=%d T=%d KS=%d dil=%d)",
+               Cin, M, T, KS, dil);
     const int mw = bm_conv_h2_mw_for(M);
     a.Mpad = bm_conv_h2_mpad(M);
     a.nchunk = cdiv(Cin, 32);

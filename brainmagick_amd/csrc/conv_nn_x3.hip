@@ -259,16 +259,12 @@ extern "C" int bm_conv1d_nn_x3(const float* x, long x_bstride, const void* wpack
                                const float* res, long res_bstride, float* y_pre, float* y_out,
                                long y_bstride, float* stats, int B, int Cin, int M, int T, int KS,
                                int dil, int act, float leak, void* stream) {
-    BM_REQUIRE(x && wpacked, "conv1d_nn_x3: null x/w");
-    BM_REQUIRE(y_pre || y_out, "conv1d_nn_x3: no output");
     BM_REQUIRE(KS == 1 || KS == 3 || KS == 5, "conv1d_nn_x3: kernel size %d not supported (1, 3, 5)", KS);
-    BM_REQUIRE(B >= 0 && Cin > 0 && M > 0 && T > 0 && dil >= 1, "conv1d_nn_x3: bad dims");
-    BM_REQUIRE((ep_scale == nullptr) == (ep_shift == nullptr), "conv1d_nn_x3: scale/shift must come together");
     ConvNNArgs a;
-    a.x = x; a.x_bstride = x_bstride; a.wp = (const float*)wpacked; a.widx = widx; a.bias = bias; a.bias_gstride = bias_gstride;
-    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.res = res; a.res_bstride = res_bstride;
-    a.y_pre = y_pre; a.y_out = y_out; a.y_bstride = y_bstride; a.stats = stats;
-    a.B = B; a.Cin = Cin; a.M = M; a.T = T; a.KS = KS; a.dil = dil; a.act = act; a.leak = leak;
+    if (int e = conv_nn_fill_args(a, "conv1d_nn_x3", x, x_bstride, (const float*)wpacked, widx, bias, bias_gstride, ep_scale,
+                                  ep_shift, res, res_bstride, y_pre, y_out, y_bstride, stats, B, Cin, M, T, KS, dil, act,
+                                  leak))
+        return e;
     const int mt = bm_conv_x3_mt_for(M);
     a.Mpad = bm_conv_x3_mpad(M);
     a.nchunk = cdiv(Cin, XC);

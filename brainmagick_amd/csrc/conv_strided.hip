@@ -245,19 +245,16 @@ static int conv_strided_common(int scatter, const float* x, long x_bstride, cons
                                const float* ep_scale, const float* ep_shift, float* y_pre, float* y_out,
                                long y_bstride, float* stats, int B, int Cin, int M, int T, int Tout, int KS,
                                int stride, int dil, int pad, int act, float leak, void* stream) {
-    BM_REQUIRE(x && wpacked, "conv_strided: null x/w");
-    BM_REQUIRE(y_pre || y_out, "conv_strided: no output");
-    BM_REQUIRE(B >= 0 && Cin > 0 && M > 0 && T > 0 && Tout > 0, "conv_strided: bad dims");
     BM_REQUIRE(KS >= 1 && stride >= 1 && dil >= 1 && pad >= 0, "conv_strided: bad geometry K=%d s=%d dil=%d pad=%d",
                KS, stride, dil, pad);
-    BM_REQUIRE((ep_scale == nullptr) == (ep_shift == nullptr), "conv_strided: scale/shift must come together");
-    BM_REQUIRE((long)M * Tout < (1L << 31) && (long)Cin * T < (1L << 31), "conv_strided: a segment exceeds 2^31 elements");
+    BM_REQUIRE(T > 0, "conv_strided: bad dims");
     ConvStridedArgs g;
     ConvNNArgs& a = g.c;
-    a.x = x; a.x_bstride = x_bstride; a.wp = wpacked; a.widx = nullptr; a.bias = bias; a.bias_gstride = 0;
-    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.res = nullptr; a.res_bstride = 0;
-    a.y_pre = y_pre; a.y_out = y_out; a.y_bstride = y_bstride; a.stats = stats;
-    a.B = B; a.Cin = Cin; a.M = M; a.T = Tout; a.KS = KS; a.dil = dil; a.act = act; a.leak = leak;
+    // a.T = the OUTPUT length; no weight groups, no residual
+    if (int e = conv_nn_fill_args(a, "conv_strided", x, x_bstride, wpacked, nullptr, bias, 0, ep_scale, ep_shift, nullptr, 0,
+                                  y_pre, y_out, y_bstride, stats, B, Cin, M, Tout, KS, dil, act, leak))
+        return e;
+    BM_REQUIRE((long)M * Tout < (1L << 31) && (long)Cin * T < (1L << 31), "conv_strided: a segment exceeds 2^31 elements");
     const int mt = strided_mt_for(M);
     a.Mpad = bm_conv_mpad(M);
     a.nchunk = cdiv(Cin, BM_BKC);

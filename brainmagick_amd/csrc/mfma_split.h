@@ -1,4 +1,4 @@
-// What the split-operand MFMA contractions (f16x2: conv_nn_h2w / conv_nn_h2d / gemm_nt_h2w; 3 x bf16: conv_nn_x3 /
+// What the split-operand MFMA contractions (f16x2: conv_nn_h2w / pack_h2 / gemm_nt_h2w; 3 x bf16: conv_nn_x3 /
 // gemm_nt_x3; staging vectors also gemm_nt) share: the scale rule, the operand splits, the buffer descriptor and the
 // compile-time loop.  Producer, packer and consumer must apply the scale rule bit for bit the same way, so it lives
 // here ONCE.  Its CPU restatements, for the tests: scripts/emulate_f16x2_split.py and scale_from_amax in

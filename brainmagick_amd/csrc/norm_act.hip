@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256, 4) void bn_bwd_fused_kernel(
     if (threadIdx.x == 0 && dy_partial) dy_partial[(long)c * nsplit + split] = acc2[0];
 }
 
-// A/B switch: 0 = the two-pass kernels, 1 = one pass (default; environment BM_BN_BWD_FUSED).
+// Test hook (bm_act_bn_bwd_set_fused): 0 = the two-pass kernels, 1 = one pass; -1 = the default, one pass.
 // Measured (profiles/r5_ab_notes.md): two passes 152-154 us stand-alone / ~118 us inside the step (the second pass
 // re-reads from the memory-side cache), one pass 113-118 us stand-alone, -0.2 ... -0.27 ms per training step.  Two more
 // forms were built, measured and removed: slabs of 5 float4 per thread with 6 workgroups per CU (119-125 us) and a
@@ -572,13 +572,7 @@ extern "C" int bm_act_bn_bwd_set_fused(int mode) {
     g_bn_bwd_fused = mode < 0 ? -1 : (mode ? 1 : 0);
     return prev;
 }
-static int fused_mode() {
-    if (g_bn_bwd_fused < 0) {
-        const char* e = getenv("BM_BN_BWD_FUSED");
-        g_bn_bwd_fused = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_bn_bwd_fused;
-}
+static int fused_mode() { return g_bn_bwd_fused != 0; }
 
 extern "C" int bm_bwd_nsplit(int B);
 // splits of the one-pass kernel: the smallest count whose per-split slab fits the registers; 0 = not covered

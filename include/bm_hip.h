@@ -129,7 +129,7 @@ int bm_gemm_nt_x3(const float* a, long a_sstride, long a_rstride, const float* x
 int bm_conv_x3_mt_for(int M);
 int bm_conv_x3_mpad(int M);
 
-/* ---- fp32-ACCURATE contraction on the f16 matrix cores, compute mode "f16x2" (conv_nn_h2w.hip): every operand
+/* ---- fp32-ACCURATE contraction on the f16 matrix cores, compute mode "f16x2" (conv_nn_h2w.hip, pack_h2.hip): every operand
  * is scaled by a power of two (per tensor for activations, per output row for weights) and split into two f16
  * planes; three partial products per MFMA block, fp32 accumulate, exact inverse scaling in the epilogue.  Half
  * the matrix-core work of "f32x3" at the same parity tolerances.  Same conv contract as bm_conv1d_nn plus
@@ -240,7 +240,7 @@ int bm_affine_act_res(const float* y, const float* scale, const float* shift, co
                       void* stream);
 int bm_bwd_nsplit(int B);
 long bm_act_bn_bwd_workspace_bytes(int B, int C);
-int bm_act_bn_bwd_set_fused(int mode);                    /* 0: two passes; 1: one pass (-1: default = 1 unless BM_BN_BWD_FUSED=0); returns the previous setting */
+int bm_act_bn_bwd_set_fused(int mode);                    /* test hook -- 0: two passes; 1: one pass (-1: the default, one pass); returns the previous setting */
 int bm_act_bn_bwd_set_poll_limit(int polls);              /* test hook: polls before a workgroup computes its partners' sums itself (-1: default) */
 long bm_act_bn_bwd_fused_fallbacks(void);                 /* debug counter (synchronises): workgroups of the one-pass kernel that gave up on a partner and computed its sums themselves */
 int bm_act_bn_bwd_fused_covers(int B, int C, int T);      /* 1: the shape is covered by the ONE-pass train-mode BatchNorm backward (slab in registers); taken when dout, y and dy are 16-byte aligned too */

@@ -12,7 +12,7 @@ import brainmagick_amd  # noqa: E402
 from brainmagick_amd import hip_ops as H  # noqa: E402
 
 B, T = 256, 360
-# (the production main loop stamps a stage as one segment; the LDS-DMA loop of conv_nn_h2d.hip had five)
+# (the production main loop stamps a stage as one segment; the LDS-DMA loop of rounds 2-5 had five)
 SEG = ["stage", "-", "-", "-", "-"]
 g = torch.Generator().manual_seed(0)
 # what the epilogue carries: y_pre alone, y_pre + BatchNorm partial sums (the forward convs of the stack), y_out +
