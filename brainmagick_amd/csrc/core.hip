@@ -20,7 +20,7 @@ int bm_check_launch(const char* what) {
 }
 
 extern "C" const char* bm_last_error(void) { return bm_err_buf; }
-extern "C" int bm_version(void) { return 114; }   // 0.1.14: the mel spectrogram (bm_wave_moments, bm_mel_spectrogram)
+extern "C" int bm_version(void) { return 115; }   // 0.1.15: the resampler and the YIN pitch (bm_resample_frac, bm_yin_pitch)
 
 // Number of HIP devices visible; <0 on error.  Lets the Python side fail loudly early.
 extern "C" int bm_device_count(void) {

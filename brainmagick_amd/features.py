@@ -20,8 +20,9 @@ Three rules, named for what they do, cover the reference's features:
   (Wav2VecTransformer, Wav2VecConvolution).
 
 Not built: WordPulse and PhonemePulse (``post_process``), Wav2VecChunk, the batch's ``_event_lists``, and computing the
-wav2vec2 hidden states / the word embeddings themselves (the mel spectrogram's arrays come from
-``audio.DeviceMelSpectrum.compute``).  There is no CPU fallback.
+wav2vec2 hidden states / the word embeddings themselves (the mel spectrogram's and the pitch's arrays come from
+``audio.DeviceMelSpectrum.compute`` and ``audio.DevicePitch.compute``, resampled to 16 kHz on the device when asked).
+There is no CPU fallback.
 """
 import collections
 import typing as tp

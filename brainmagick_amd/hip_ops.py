@@ -1912,6 +1912,13 @@ def _wave_moments(table, lengths, device) -> torch.Tensor:
     return mom
 
 
+def _moments_arg(moments, n: int, device, what: str) -> torch.Tensor:
+    _req(moments, f"{what}: moments", torch.float64)
+    if tuple(moments.shape) != (n, 2) or moments.device != device:
+        raise BmHipError(f"{what}: moments of shape {tuple(moments.shape)} on {moments.device}; expected [{n}, 2] on {device}")
+    return moments
+
+
 def wave_moments(waves: tp.Sequence[torch.Tensor]) -> torch.Tensor:
     """``[n, 2]`` float64 on the device: ``(mean, 1 / (1e-8 + unbiased std))`` of every 1-D fp32 device waveform, in fp64,
     ONE launch for all of them and no host read-back -- the ``(shift, scale)`` of MelSpectrum's ``norm_audio``."""
@@ -1924,11 +1931,13 @@ def wave_moments(waves: tp.Sequence[torch.Tensor]) -> torch.Tensor:
 
 def mel_spectrograms(waves: tp.Sequence[torch.Tensor], n_mels: int = 40, n_fft: int = 512, in_sampling: int = 16_000,
                      normalized: bool = True, use_log_scale: bool = True, log_scale_eps: float = 1e-5,
-                     norm_audio: bool = True) -> tp.List[torch.Tensor]:
+                     norm_audio: bool = True, moments: tp.Optional[torch.Tensor] = None) -> tp.List[torch.Tensor]:
     """What ``MelSpectrum._compute`` (bm/features/audio.py:61-76) returns for every mono waveform at ``in_sampling``:
     a list of ``[n_mels, 1 + L // (n_fft // 4)]`` fp32 tensors, carved from one allocation.  ``waves``: 1-D fp32 device
     tensors, read in place (4-byte alignment is all that is assumed).  Two launches for the whole list (one with
-    ``norm_audio=False``): the statistics, then framing, reflect padding, window, DFT, power, filterbank and log."""
+    ``norm_audio=False``): the statistics, then framing, reflect padding, window, DFT, power, filterbank and log.
+    ``moments`` (``[n, 2]`` float64 on the device, ``(shift, scale)`` per waveform): used as they are instead of the
+    statistics launch, whatever ``norm_audio`` says -- waveforms that were normalised before they were resampled."""
     mel_check_limits(n_fft, n_mels)
     waves = _wave_list(waves, "mel_spectrograms", n_fft // 2)
     if not waves:
@@ -1943,11 +1952,196 @@ def mel_spectrograms(waves: tp.Sequence[torch.Tensor], n_mels: int = 40, n_fft: 
         outs.append(flat[at:at + n_mels * f].view(n_mels, f))
         at += n_mels * f
     table, lengths = _wave_table(waves, outs)
-    mom = _wave_moments(table, lengths, device) if norm_audio else None
+    if moments is not None:
+        mom = _moments_arg(moments, len(waves), device, "mel_spectrograms")
+    else:
+        mom = _wave_moments(table, lengths, device) if norm_audio else None
 
     def launch():
         check(lib().bm_mel_spectrogram(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), _p(mom), _p(basis),
                                        n_fft, nbp, _p(fbw), _p(rng), ctypes.c_void_p(rng_host.ctypes.data), n_mels,
                                        int(bool(use_log_scale)), float(log_scale_eps), _stream()), "bm_mel_spectrogram")
     _timed("mel_spectrogram", 4. * n_fft * nbp * sum(frames), launch)
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------
+# julius.resample.ResampleFrac over resident waveforms (csrc/resample.hip; bm/features/audio.py:66, 113, 186).  julius is
+# not part of this stack: the filter is restated from its published definition, with julius' own fp32 torch expressions.
+RESAMPLE_MAX_NEW, RESAMPLE_MAX_SPAN = 4096, 16384      # phases; floats of LDS that 16 frames cover: 15 old + ntaps (to 4)
+_resample_taps: tp.Dict[tp.Any, tp.Any] = {}
+
+
+def resample_ratio(old_sr: int, new_sr: int) -> tp.Tuple[int, int]:
+    """``(old, new)``: the two rates divided by their gcd.  Integer rates of at least 1 Hz, else ``ValueError``."""
+    import math
+    for name, sr in (("old_sr", old_sr), ("new_sr", new_sr)):
+        if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr < 1:
+            raise ValueError(f"resample: {name} = {sr!r}; the rates are integers of at least 1 Hz")
+    g = math.gcd(int(old_sr), int(new_sr))
+    return int(old_sr) // g, int(new_sr) // g
+
+
+def resample_check_limits(old: int, new: int, width: int) -> None:
+    """``ValueError`` naming the limit that the reduced ratio ``old / new`` with ``width`` is outside of."""
+    ntp = (2 * width + old + 3) // 4 * 4
+    if new > RESAMPLE_MAX_NEW:
+        raise ValueError(f"resample: {new} phases (new_sr / gcd); the kernel takes at most {RESAMPLE_MAX_NEW}")
+    if 15 * old + ntp > RESAMPLE_MAX_SPAN:
+        raise ValueError(f"resample: ratio {old} / {new} with {2 * width + old} taps: 16 frames cover 15 * old + ntaps = "
+                         f"{15 * old + ntp} samples, the LDS span holds at most {RESAMPLE_MAX_SPAN}")
+
+
+def resample_taps(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945, device=None):
+    """``(taps, old, new, width)``: the ``[new, 2 * width + old]`` fp32 table of julius' ``ResampleFrac(old_sr, new_sr,
+    zeros, rolloff)`` -- phase ``i`` is a sinc at ``min(old, new) * rolloff`` under a ``cos^2`` window of ``zeros`` zero
+    crossings, normalised to a sum of 1 -- computed on the CPU with julius' own fp32 torch expressions.  With ``device``
+    the first element is the kernel's table instead: ``[ntaps to a multiple of 4, new to a multiple of 16]`` on that
+    device, tap-major, zero-padded.  Cached per (old, new, zeros, rolloff, device).  ``old == new``: ``ValueError`` (the
+    identity has no filter)."""
+    import math
+    old, new = resample_ratio(old_sr, new_sr)
+    if old == new:
+        raise ValueError(f"resample: {old_sr} Hz -> {new_sr} Hz is the identity; it has no filter")
+    if isinstance(zeros, bool) or not isinstance(zeros, int) or zeros < 1:
+        raise ValueError(f"resample: zeros = {zeros!r}; a positive integer")
+    if not 0. < float(rolloff) <= 1.:
+        raise ValueError(f"resample: rolloff = {rolloff!r}; 0 < rolloff <= 1")
+    device = torch.device(device) if device is not None else None
+    key = (old, new, zeros, float(rolloff), device)
+    hit = _resample_taps.get(key)
+    if hit is not None:
+        return hit
+    sr = min(old, new) * rolloff
+    width = math.ceil(zeros * old / sr)
+    resample_check_limits(old, new, width)
+    if device is not None:
+        taps = resample_taps(old_sr, new_sr, zeros, rolloff)[0]
+        ntaps = taps.shape[1]
+        packed = torch.zeros((ntaps + 3) // 4 * 4, (new + 15) // 16 * 16, dtype=torch.float32)
+        packed[:ntaps, :new] = taps.t()
+        hit = (packed.to(device), old, new, width)
+    else:
+        idx = torch.arange(-width, width + old).float()
+        rows = []
+        for i in range(new):
+            t = (-i / new + idx / old) * sr
+            t.clamp_(-zeros, zeros)
+            t *= math.pi
+            window = torch.cos(t / zeros / 2) ** 2
+            kernel = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t) * window
+            kernel.div_(kernel.sum())
+            rows.append(kernel)
+        taps = torch.stack(rows)
+        assert taps.dtype == torch.float32 and tuple(taps.shape) == (new, 2 * width + old)
+        hit = (taps, old, new, width)
+    if len(_resample_taps) >= 64:
+        _resample_taps.clear()
+    _resample_taps[key] = hit
+    return hit
+
+
+def resample_length(length: int, old: int, new: int) -> int:
+    """``floor(new * length / old)`` in integers (julius forms it through a default-dtype tensor)."""
+    return new * int(length) // old
+
+
+def resample_frames_tile(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945) -> int:
+    """julius frames (``new`` outputs each, ``old`` inputs apart) that one workgroup of ``bm_resample_frac`` owns."""
+    _, old, new, width = resample_taps(old_sr, new_sr, zeros, rolloff)
+    return int(lib().bm_resample_frames_tile(old, new, width))
+
+
+def resample_frac(waves: tp.Sequence[torch.Tensor], old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945,
+                  moments: tp.Optional[torch.Tensor] = None) -> tp.List[torch.Tensor]:
+    """``julius.resample.ResampleFrac(old_sr, new_sr, zeros, rolloff)(wave)`` for every 1-D fp32 device waveform, all at
+    ``old_sr``: a list of 1-D fp32 tensors of ``floor(new * L / old)`` samples, carved from one allocation, ONE launch
+    (``bm_resample_frac``).  Equal rates return the waveforms themselves, as julius does.  ``moments`` (``[n, 2]``
+    float64 on the device, what ``wave_moments`` gives): every sample enters as ``(x - mean) * inv`` in fp64, rounded once
+    -- the reference normalises at the source rate.  Limits (``ValueError`` before any launch): ``new <= 4096`` phases,
+    ``15 * old + ntaps <= 16384`` staged samples, ``L < 2^31`` in and out, 65535 waveforms."""
+    old, new = resample_ratio(old_sr, new_sr)
+    waves = list(waves)
+    if old == new:
+        if moments is not None:
+            raise ValueError("resample_frac: equal rates return the waveforms as they are; moments cannot be applied")
+        return _wave_list(waves, "resample_frac")
+    _, _, _, width = resample_taps(old_sr, new_sr, zeros, rolloff)              # the limits first: they need no device
+    for i, x in enumerate(waves):
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and resample_length(x.numel(), old, new) >= 2 ** 31:
+            raise ValueError(f"resample_frac: waveform {i} of {x.numel()} samples gives "
+                             f"{resample_length(x.numel(), old, new)} outputs; the kernel takes fewer than 2^31")
+    waves = _wave_list(waves, "resample_frac")
+    if not waves:
+        return []
+    device = waves[0].device
+    taps = resample_taps(old_sr, new_sr, zeros, rolloff, device)[0]
+    mom = _moments_arg(moments, len(waves), device, "resample_frac") if moments is not None else None
+    lens = [resample_length(x.numel(), old, new) for x in waves]
+    flat = torch.empty(sum(lens), dtype=torch.float32, device=device)
+    outs, at = [], 0
+    for n in lens:
+        outs.append(flat[at:at + n])
+        at += n
+    table, lengths = _wave_table(waves, outs)
+
+    def launch():
+        check(lib().bm_resample_frac(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), _p(mom), _p(taps), old,
+                                     new, width, _stream()), "bm_resample_frac")
+    _timed("resample_frac", 2. * (2 * width + old) * sum(lens), launch)
+    return outs
+
+
+# The Pitch feature (csrc/pitch.hip; bm/features/audio.py:110-124, bm/lib/pitch_calc/yin.py).
+YIN_MAX_WLEN, YIN_MAX_WSTEP = 1024, 512
+
+
+def yin_taus(sr: float, w_len: int, w_step: int, f0_min: float, f0_max: float) -> tp.Tuple[int, int]:
+    """``(tau_min, tau_max) = (int(sr / f0_max), int(sr / f0_min))`` behind every limit's ``ValueError``."""
+    if not (isinstance(w_len, int) and 2 <= w_len <= YIN_MAX_WLEN):
+        raise ValueError(f"yin_pitch: w_len = {w_len!r}; the kernel takes 2 <= w_len <= {YIN_MAX_WLEN}")
+    if not (isinstance(w_step, int) and 1 <= w_step <= YIN_MAX_WSTEP):
+        raise ValueError(f"yin_pitch: w_step = {w_step!r}; the kernel takes 1 <= w_step <= {YIN_MAX_WSTEP}")
+    if not (sr > 0 and f0_min > 0 and f0_max > 0):
+        raise ValueError(f"yin_pitch: sr = {sr}, f0_min = {f0_min}, f0_max = {f0_max}; all three are positive")
+    tau_min, tau_max = int(sr / f0_max), int(sr / f0_min)
+    if tau_min < 1:
+        raise ValueError(f"yin_pitch: tau_min = int(sr / f0_max) = {tau_min}; f0_max = {f0_max} is above sr = {sr}")
+    if tau_max > w_len:
+        raise ValueError(f"yin_pitch: tau_max = int(sr / f0_min) = {tau_max} is above w_len = {w_len}")
+    return tau_min, tau_max
+
+
+def yin_frames(length: int, w_len: int, w_step: int) -> int:
+    return len(range(0, int(length) - w_len, w_step))
+
+
+def yin_pitch(waves: tp.Sequence[torch.Tensor], sr: float = 16_000, w_len: int = 256, w_step: int = 64,
+              harmo_thresh: float = 0.1, f0_min: float = 100.0, f0_max: float = 350.0) -> tp.List[torch.Tensor]:
+    """The ``pitches`` of ``compute_yin(sig, sr, w_len, w_step, f0_min, f0_max, harmo_thresh)`` for every 1-D fp32 device
+    waveform: a list of ``[1, len(range(0, L - w_len, w_step))]`` fp32 tensors carved from one allocation, ONE launch
+    (``bm_yin_pitch``): the difference function as a direct fp64 sum, its cumulative mean normalisation, the first dip
+    under the threshold walked to its bottom, ``sr / tau``; 0.0 for an unvoiced, a silent or a non-finite frame.
+    ``ValueError``: ``L <= w_len``, ``tau_max > w_len``, ``tau_min < 1``, ``w_len > 1024``, ``w_step > 512``."""
+    tau_min, tau_max = yin_taus(sr, w_len, w_step, f0_min, f0_max)
+    waves = list(waves)
+    for i, x in enumerate(waves):                               # the limits first: they need no device
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() <= w_len:
+            raise ValueError(f"yin_pitch: waveform {i} has {x.numel()} samples; a frame needs L > w_len = {w_len}")
+    waves = _wave_list(waves, "yin_pitch")
+    if not waves:
+        return []
+    device = waves[0].device
+    frames = [yin_frames(x.numel(), w_len, w_step) for x in waves]
+    flat = torch.empty(sum(frames), dtype=torch.float32, device=device)
+    outs, at = [], 0
+    for f in frames:
+        outs.append(flat[at:at + f].view(1, f))
+        at += f
+    table, lengths = _wave_table(waves, outs)
+
+    def launch():
+        check(lib().bm_yin_pitch(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), float(sr), w_len, w_step,
+                                 tau_min, tau_max, float(harmo_thresh), _stream()), "bm_yin_pitch")
+    _timed("yin_pitch", 3. * w_len * tau_max * sum(frames), launch)
     return outs

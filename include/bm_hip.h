@@ -504,6 +504,39 @@ int bm_mel_spectrogram(const void* table, const long* lengths, int n_waves, cons
                        int n_fft, int nbp, const float* fbw, const int* range, const int* range_host, int n_mels,
                        int use_log, float eps, void* stream);
 
+/* ---- julius' fractional resampler over resident waveforms (resample.hip)  bm/features/audio.py:66, 113, 186 ----
+ * julius.resample.ResampleFrac(old_sr, new_sr, zeros, rolloff) RESTATED from its published definition, ONE launch for
+ * every waveform of one reduced ratio old_rate / new_rate (already divided by their gcd, old_rate != new_rate):
+ *     out[f new + i] = sum_k taps[i][k] padded[f old + k],  k < ntaps = 2 width + old,  f new + i < floor(new L / old),
+ * `padded` the waveform replicate-padded by width samples on the left and width + old on the right (indexed in place: no
+ * padded copy).  table: mel.hip's entries (bm_mel_table_fill), `out` the floor(new L / old) outputs of the waveform;
+ * lengths (HOST memory): the same lengths.  mom: null, or what bm_wave_moments wrote for the same table: a sample
+ * enters as (float)(((double)x - shift) * scale).  taps: [ntp][newp] fp32, taps[k][i] the tap k of phase i, ntp = ntaps
+ * rounded up to 4 and newp = new rounded up to 16, zero beyond ntaps and beyond new.  Grid (tile of
+ * bm_resample_frames_tile frames, waveform); the samples a tile covers are staged in LDS once.  new >= 16:
+ * v_mfma_f32_16x16x4_f32, 16 frames x 16 phases per wavefront, one accumulator chain with k ascending; new < 16: one
+ * fmaf chain per output with k ascending.  A ratio always takes the same variant: an output's bits do not depend on its
+ * tile, the grid or the other waveforms.  Every output is stored exactly once, no atomics.
+ * Limits (BM_ERR_ARG; bm_resample_frames_tile returns 0): new <= 4096 and 15 old + ntp <= 16384 floats (the 64 KiB of
+ * LDS that 16 frames cover); 1 <= L < 2^31 and floor(new L / old) < 2^31; n_waves <= 65535. */
+int bm_resample_frames_tile(int old_rate, int new_rate, int width);
+int bm_resample_frac(const void* table, const long* lengths, int n_waves, const double* mom, const float* taps,
+                     int old_rate, int new_rate, int width, void* stream);
+
+/* ---- the Pitch feature from resident waveforms (pitch.hip)  bm/features/audio.py:110-124, bm/lib/pitch_calc/yin.py ----
+ * compute_yin(sig, sr, w_len, w_step, f0_min, f0_max, harmo_thresh)[0] as ONE launch: frame t < ceil((L - w_len) /
+ * w_step) starts at t w_step;  d(tau) = sum_{j < w_len - tau} (x_j - x_{j + tau})^2  in fp64 with j ascending (the
+ * reference's FFT expression as a sum);  c(0) = 0, c(tau) = d(tau) tau / sum_{1..tau} d  with the running sum in
+ * ascending tau;  the first tau in [tau_min, tau_max) with c < thresh, walked down while c(tau + 1) < c(tau) and tau + 1 <
+ * tau_max;  out[t] = (float)(sr / tau), or 0.f when there is none.  A silent frame (0 / 0) and a frame holding a NaN or
+ * an Inf give 0.f.  table: mel.hip's entries, `out` the waveform's frames; lengths (HOST memory).  Grid (tile of
+ * bm_yin_frames_tile frames, waveform), one wavefront per frame, samples staged in LDS once; no atomics.
+ * Limits (BM_ERR_ARG): w_len < L < 2^31, 2 <= w_len <= 1024, 1 <= w_step <= 512, 1 <= tau_min, tau_max <= w_len,
+ * n_waves <= 65535. */
+int bm_yin_frames_tile(void);
+int bm_yin_pitch(const void* table, const long* lengths, int n_waves, double sr, int w_len, int w_step, int tau_min,
+                 int tau_max, double thresh, void* stream);
+
 /* ---- FeatureDecodingLoss and ClassificationAcc (regress.hip) bm/losses.py:117-173, bm/metrics.py:173-180 ----
  * est: fp32 [B][C][T] (the model output), out: fp32 [B][Co][T] (the features), mask: null (all true) or bytes
  * [B][1][T].  table (HOST memory): n_features rows {kind, est_start, width, out_start, weight_off}: kind 0 = continuous
