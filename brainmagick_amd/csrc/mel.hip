@@ -4,8 +4,8 @@
 // from its documentation: torch.stft(center=True, pad_mode="reflect", periodic Hann window of n_fft, onesided), divided
 // by sqrt(sum w^2) when normalized, |.|^2, times melscale_fbanks(htk, norm=None, f_min 0, f_max sr / 2).
 //
-// A table entry is {address, length, address of the [n_mels][frames] output} of one 1-D fp32 waveform, read in place
-// (4-byte alignment is all that is assumed: scalar loads, ONE summation order whatever the alignment).
+// The waveforms come in a wave table (bm_wave.h; this unit holds its two host entry points), `out` the [n_mels][frames]
+// output of a waveform; they are read with scalar loads, ONE summation order whatever the alignment.
 //
 // bm_wave_moments    grid (split, waveform), ONE launch.  A waveform of L samples is cut into ns(L) = at most MM_SPLITS
 //     splits of at least MM_MIN_SPLIT samples (a function of L alone: the bits of a waveform's moments do not depend on
@@ -33,6 +33,7 @@
 //      the lanes, so a wavefront stores runs of a row.
 // No atomics, every output element is stored exactly once.
 #include "bm_block.h"
+#include "bm_wave.h"
 
 #define ML_THREADS 256
 #define ML_WAVES (ML_THREADS / 64)
@@ -42,22 +43,15 @@
 #define ML_MAX_NFFT 2048
 #define ML_MAX_MELS 256
 #define ML_WIDE_NFFT 1024               // up to here a workgroup owns 32 frames, beyond it 16 (LDS)
-#define ML_MAX_WAVES 65535
 #define MM_SPLITS 256
 #define MM_MIN_SPLIT 16384
 
-struct MelWave {
-    const float* x;
-    float* out;
-    long L;
-};
+extern "C" long bm_wave_table_entry_bytes(void) { return (long)sizeof(BmWave); }
 
-extern "C" long bm_mel_table_entry_bytes(void) { return (long)sizeof(MelWave); }
-
-extern "C" int bm_mel_table_fill(void* entry, const float* x, long L, float* out) {
-    BM_REQUIRE(entry && x && L >= 1 && L < (1L << 31), "mel table: bad waveform (%ld samples; 1 <= L < 2^31)", L);
-    BM_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 3) == 0, "mel table: a waveform or an output is not 4-byte aligned");
-    MelWave* e = (MelWave*)entry;
+extern "C" int bm_wave_table_fill(void* entry, const float* x, long L, float* out) {
+    BM_REQUIRE(entry && x && L >= 1 && L < (1L << 31), "wave table: bad waveform (%ld samples; 1 <= L < 2^31)", L);
+    BM_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 3) == 0, "wave table: a waveform or an output is not 4-byte aligned");
+    BmWave* e = (BmWave*)entry;
     e->x = x;
     e->out = out;
     e->L = L;
@@ -80,12 +74,12 @@ __host__ __device__ __forceinline__ int mm_splits(int L) {
 
 extern "C" int bm_wave_moments_splits(long L) { return L >= 1 && L < (1L << 31) ? mm_splits((int)L) : 0; }
 
-__global__ __launch_bounds__(ML_THREADS) void wave_moments_kernel(const MelWave* __restrict__ table, int max_splits,
+__global__ __launch_bounds__(ML_THREADS) void wave_moments_kernel(const BmWave* __restrict__ table, int max_splits,
                                                                   unsigned* tickets, double* part /* [W][max_splits][2] */,
                                                                   double* __restrict__ mom /* [W][2] */) {
     __shared__ BmFoldLds<double, ML_WAVES> sh;
     const int w = blockIdx.y, split = blockIdx.x;
-    const MelWave e = table[w];
+    const BmWave e = table[w];
     const int L = (int)e.L;
     const int per = mm_per_split(L), ns = mm_splits(L);
     if (split >= ns || ns > max_splits) return;                 // uniform over the workgroup (the second: never, on a checked table)
@@ -126,28 +120,21 @@ __global__ __launch_bounds__(ML_THREADS) void wave_moments_kernel(const MelWave*
 
 extern "C" int bm_wave_moments(const void* table, const long* lengths, int n_waves, unsigned* tickets, double* part,
                                int max_splits, double* mom, void* stream) {
-    BM_REQUIRE(n_waves >= 0 && n_waves <= ML_MAX_WAVES, "wave_moments: %d waveforms, the limit is %d", n_waves, ML_MAX_WAVES);
-    if (n_waves == 0) return BM_OK;
-    BM_REQUIRE(table && lengths && tickets && part && mom, "wave_moments: null pointer");
+    const long need = bm_wave_tiles("wave_moments", table, lengths, n_waves, 0, "", [](long L) { return mm_splits((int)L); });
+    if (need <= 0) return (int)-need;                           // no waveform, or the error
+    BM_REQUIRE(tickets && part && mom, "wave_moments: null pointer");
     BM_REQUIRE((((uintptr_t)part | (uintptr_t)mom) & 7) == 0, "wave_moments: the partials or the result are not 8-byte aligned");
-    int need = 0;                                               // lengths (HOST memory): the table's own, for the grid
-    for (int w = 0; w < n_waves; ++w) {
-        BM_REQUIRE(lengths[w] >= 1 && lengths[w] < (1L << 31), "wave_moments: waveform %d has %ld samples (1 <= L < 2^31)", w,
-                   lengths[w]);
-        const int ns = mm_splits((int)lengths[w]);
-        need = ns > need ? ns : need;
-    }
     if (max_splits < need)
-        return bm_set_error(BM_ERR_WORKSPACE, "wave_moments: room for %d splits per waveform, %d needed", max_splits, need);
-    hipLaunchKernelGGL(wave_moments_kernel, dim3(need, n_waves), dim3(ML_THREADS), 0, (hipStream_t)stream,
-                       (const MelWave*)table, max_splits, tickets, part, mom);
+        return bm_set_error(BM_ERR_WORKSPACE, "wave_moments: room for %d splits per waveform, %ld needed", max_splits, need);
+    hipLaunchKernelGGL(wave_moments_kernel, dim3((unsigned)need, n_waves), dim3(ML_THREADS), 0, (hipStream_t)stream,
+                       (const BmWave*)table, max_splits, tickets, part, mom);
     return bm_check_launch("wave_moments");
 }
 
 // ---- the mel spectrogram ---------------------------------------------------------------------------------------------
 struct MelArgs {
-    const MelWave* table;
-    const double* mom;                  // [W][2] (shift, scale), or null: (0, 1)
+    const BmWave* table;
+    const double* mom;                  // [W][2]: bm_wave_norm
     const float* basis;                 // [n_fft][2 nbp]: columns [0, nbp) re, [nbp, 2 nbp) im; bins >= nb are zero
     const float* fbw;                   // [n_mels][nb]
     const int* range;                   // [n_mels][2]: lo, hi
@@ -165,34 +152,24 @@ __global__ __launch_bounds__(ML_THREADS) void mel_spectrogram_kernel(const MelAr
     const int N = g.n_fft, hop = N >> 2, pitch = hop + ML_PAD;
     float* span = smem;
     float* pw = smem + (((FT + 3) * pitch + 3) & ~3);           // [nbp][FTP]
-    const MelWave e = g.table[blockIdx.y];
+    const BmWave e = g.table[blockIdx.y];
     const int L = (int)e.L;
     const int frames = 1 + L / hop;
     const int f0 = blockIdx.x * FT;
     if (f0 >= frames) return;                                   // uniform: a shorter waveform of the table
     const int nf = min(FT, frames - f0);
     const int tid = threadIdx.x;
-    double shift = 0.0, scale = 1.0;
-    if (g.mom) {
-        shift = g.mom[2 * blockIdx.y];
-        scale = g.mom[2 * blockIdx.y + 1];
-    }
+    const BmWaveNorm norm = bm_wave_norm(g.mom, blockIdx.y);
 
-    // 1: local sample i is sample g0 + i of the waveform padded by n_fft / 2 reflected samples on both sides.  With
-    // L > n_fft / 2 one reflection lands inside [0, L); the clamp behind it never moves a validated index.
+    // 1: local sample i is sample g0 + i of the waveform padded by n_fft / 2 reflected samples on both sides (with
+    // L > n_fft / 2 one reflection lands inside [0, L)).
     const long g0 = (long)f0 * hop - (N >> 1);
     const int nvalid = (nf + 3) * hop;
     const float* __restrict__ x = e.x;
     for (int i = tid; i < (FT + 3) * hop; i += ML_THREADS) {
         const int c = (int)bm_div((unsigned)i, g.div_hop);
         float v = 0.f;
-        if (i < nvalid) {
-            long s = g0 + i;
-            s = s < 0 ? -s : s;
-            s = s >= L ? 2L * (L - 1) - s : s;
-            s = s < 0 ? 0 : s > L - 1 ? L - 1 : s;
-            v = (float)(((double)x[s] - shift) * scale);
-        }
+        if (i < nvalid) v = bm_wave_normed(x[bm_wave_reflect(g0 + i, L)], norm);
         span[c * pitch + (i - c * hop)] = v;
     }
     __syncthreads();
@@ -312,27 +289,19 @@ extern "C" int bm_mel_spectrogram(const void* table, const long* lengths, int n_
     BM_REQUIRE(n_fft >= ML_MIN_NFFT && n_fft <= ML_MAX_NFFT && n_fft % 4 == 0,
                "mel_spectrogram: n_fft = %d (%d <= n_fft <= %d, a multiple of 4)", n_fft, ML_MIN_NFFT, ML_MAX_NFFT);
     BM_REQUIRE(n_mels >= 1 && n_mels <= ML_MAX_MELS, "mel_spectrogram: n_mels = %d (1 <= n_mels <= %d)", n_mels, ML_MAX_MELS);
-    BM_REQUIRE(n_waves >= 0 && n_waves <= ML_MAX_WAVES, "mel_spectrogram: %d waveforms, the limit is %d", n_waves, ML_MAX_WAVES);
-    const int nb = n_fft / 2 + 1, hop = n_fft / 4;
+    const int nb = n_fft / 2 + 1, hop = n_fft / 4, FT = bm_mel_frame_tile(n_fft);
     BM_REQUIRE(nbp == ((nb + 15) & ~15), "mel_spectrogram: the basis has %d bin columns, expected %d", nbp, (nb + 15) & ~15);
-    if (n_waves == 0) return BM_OK;
-    BM_REQUIRE(table && lengths && basis && fbw && range && range_host, "mel_spectrogram: null pointer");
+    const long tiles = bm_wave_tiles("mel_spectrogram", table, lengths, n_waves, n_fft / 2, "the reflect padding: n_fft / 2 = ",
+                                     [=](long L) { return (1 + L / hop + FT - 1) / FT; });
+    if (tiles <= 0) return (int)-tiles;                         // no waveform, or the error
+    BM_REQUIRE(basis && fbw && range && range_host, "mel_spectrogram: null pointer");
     BM_REQUIRE(((uintptr_t)mom & 7) == 0 && (((uintptr_t)basis | (uintptr_t)fbw | (uintptr_t)range) & 3) == 0,
                "mel_spectrogram: a table is not aligned");
     for (int m = 0; m < n_mels; ++m)                            // range_host (HOST memory): the same rows as `range`
         BM_REQUIRE(range_host[2 * m] >= 0 && range_host[2 * m] <= range_host[2 * m + 1] && range_host[2 * m + 1] <= nb,
                    "mel_spectrogram: filter %d covers the bins [%d, %d) of %d", m, range_host[2 * m], range_host[2 * m + 1], nb);
-    long tiles = 0;
-    const int FT = bm_mel_frame_tile(n_fft);
-    for (int w = 0; w < n_waves; ++w) {
-        BM_REQUIRE(lengths[w] > n_fft / 2 && lengths[w] < (1L << 31),
-                   "mel_spectrogram: waveform %d has %ld samples (n_fft / 2 = %d < L < 2^31: the reflect padding)", w,
-                   lengths[w], n_fft / 2);
-        const long t = (1 + lengths[w] / hop + FT - 1) / FT;
-        tiles = t > tiles ? t : tiles;
-    }
     MelArgs g;
-    g.table = (const MelWave*)table;
+    g.table = (const BmWave*)table;
     g.mom = mom;
     g.basis = basis;
     g.fbw = fbw;

@@ -8,29 +8,22 @@
 // and the pitch is 0; a frame that holds a NaN or an Inf has a running sum that is not finite from tau = 1 on (d(1) covers
 // every sample), its c is NaN throughout -- what the reference's FFT makes of it -- and its pitch is 0.
 //
-// A table entry is mel.hip's {address, output, length}.  Grid (tile of YN_FT frames, waveform); a workgroup (256 threads)
-// stages the (YN_FT - 1) w_step + w_len samples of its frames in LDS once, as doubles; ONE wavefront per frame:
+// A wave table (bm_wave.h), `out` the frames of a waveform.  Grid (tile of YN_FT frames, waveform); a workgroup (256
+// threads) stages the (YN_FT - 1) w_step + w_len samples of its frames in LDS once, as doubles; ONE wavefront per frame:
 //   1. lanes over tau, 64 at a time: d(tau) in fp64 by fma with j ascending;
 //   2. the running sum over the 64 lanes one after the other (tau ascending, the order of numpy's cumsum), carried from
 //      one group of 64 to the next; c(tau) into the wavefront's row of LDS;
 //   3. the first tau under the threshold by ballot, the walk down by reading c.
 // No atomics, every output element is stored exactly once.
-#include "bm_common.h"
+#include "bm_wave.h"
 
 #define YN_THREADS 256
 #define YN_FT (YN_THREADS / 64)         // frames per workgroup: one per wavefront
 #define YN_MAX_WLEN 1024
 #define YN_MAX_WSTEP 512
-#define YN_MAX_WAVES 65535
-
-struct YnWave {                         // mel.hip's table entry (bm_mel_table_fill)
-    const float* x;
-    float* out;
-    long L;
-};
 
 struct YnArgs {
-    const YnWave* table;
+    const BmWave* table;
     double sr, thresh;
     int w_len, w_step, tau_min, tau_max;
 };
@@ -46,7 +39,7 @@ __device__ __forceinline__ double yn_readlane(double v, int lane) {
 
 __global__ __launch_bounds__(YN_THREADS) void yin_pitch_kernel(const YnArgs g) {
     extern __shared__ __attribute__((aligned(16))) double ysm[];
-    const YnWave e = g.table[blockIdx.y];
+    const BmWave e = g.table[blockIdx.y];
     const long L = e.L;
     const long frames = (L - g.w_len + g.w_step - 1) / g.w_step;
     const long f0 = (long)blockIdx.x * YN_FT;
@@ -109,19 +102,11 @@ extern "C" int bm_yin_pitch(const void* table, const long* lengths, int n_waves,
     BM_REQUIRE(tau_min >= 1 && tau_max <= w_len, "yin_pitch: tau_min = %d, tau_max = %d (1 <= tau_min, tau_max <= w_len = %d)",
                tau_min, tau_max, w_len);
     BM_REQUIRE(sr > 0, "yin_pitch: sr = %g", sr);
-    BM_REQUIRE(n_waves >= 0 && n_waves <= YN_MAX_WAVES, "yin_pitch: %d waveforms, the limit is %d", n_waves, YN_MAX_WAVES);
-    if (n_waves == 0) return BM_OK;
-    BM_REQUIRE(table && lengths, "yin_pitch: null pointer");
-    long tiles = 0;
-    for (int w = 0; w < n_waves; ++w) {                         // lengths (HOST memory): the table's own, for the grid
-        BM_REQUIRE(lengths[w] > w_len && lengths[w] < (1L << 31), "yin_pitch: waveform %d has %ld samples (w_len = %d < L < 2^31)",
-                   w, lengths[w], w_len);
-        const long frames = (lengths[w] - w_len + w_step - 1) / w_step;
-        const long t = (frames + YN_FT - 1) / YN_FT;
-        tiles = t > tiles ? t : tiles;
-    }
+    const long tiles = bm_wave_tiles("yin_pitch", table, lengths, n_waves, w_len, "w_len = ",
+                                     [=](long L) { return ((L - w_len + w_step - 1) / w_step + YN_FT - 1) / YN_FT; });
+    if (tiles <= 0) return (int)-tiles;                         // no waveform, or the error
     YnArgs g;
-    g.table = (const YnWave*)table;
+    g.table = (const BmWave*)table;
     g.sr = sr;
     g.thresh = thresh;
     g.w_len = w_len;

@@ -6,8 +6,8 @@
 // `width + old` on the right:
 //     out[f new + i] = sum_k taps[i][k] * padded[f old + k],   f < L / old + 1,  f new + i < floor(new L / old).
 //
-// A table entry is mel.hip's {address, output, length} of one 1-D fp32 waveform, read in place (4-byte alignment is all
-// that is assumed).  Grid (tile of FT julius frames, waveform); a workgroup (256 threads)
+// The waveforms come in a wave table (bm_wave.h), `out` the outputs of a waveform.  Grid (tile of FT julius frames,
+// waveform); a workgroup (256 threads)
 //   1. stages the (FT - 1) old + ntp padded samples its frames cover in LDS once, replicate-indexed (no padded copy of
 //      the waveform exists), normalised as (float)(((double)x - shift) * scale) when moments are given (the reference
 //      normalises at the source rate, before it resamples);
@@ -19,25 +19,18 @@
 //      new < 16: one thread per output, fmaf over k ascending from 0.f (the same staging, the same table).
 // A ratio always takes the same variant and the same FT (bm_resample_frames_tile).  Every output element is stored exactly
 // once, no atomics.
-#include "bm_common.h"
+#include "bm_wave.h"
 
 #define RS_THREADS 256
 #define RS_WAVES (RS_THREADS / 64)
 #define RS_MAX_SPAN 16384               // floats of LDS (64 KiB) that 16 frames may cover: 15 old + ntp
 #define RS_MAX_NEW 4096
-#define RS_MAX_WAVES 65535
 #define RS_FMA_SPAN 8192                // floats that a tile of the few-phase variant stages at most
 #define RS_FMA_MAX_FT 1024
 
-struct RsWave {                         // mel.hip's table entry (bm_mel_table_fill)
-    const float* x;
-    float* out;
-    long L;
-};
-
 struct RsArgs {
-    const RsWave* table;
-    const double* mom;                  // [W][2] (shift, scale), or null: (0, 1)
+    const BmWave* table;
+    const double* mom;                  // [W][2] (bm_wave_norm), or null: the samples as they are
     const float* taps;                  // [ntp][newp]
     int old_, new_, newp, width, ntaps, ntp, ft;
     BmFastDiv div_new;
@@ -59,27 +52,22 @@ extern "C" int bm_resample_frames_tile(int old_rate, int new_rate, int width) {
     return rs_frames_tile(old_rate, new_rate, width);
 }
 
-__device__ __forceinline__ void rs_stage(const RsArgs& g, const RsWave& e, int f0, float* span) {
+__device__ __forceinline__ void rs_stage(const RsArgs& g, const BmWave& e, int f0, float* span) {
     const long L = e.L;
-    double shift = 0.0, scale = 1.0;
-    if (g.mom) {
-        shift = g.mom[2 * blockIdx.y];
-        scale = g.mom[2 * blockIdx.y + 1];
-    }
-    const long g0 = (long)f0 * g.old_ - g.width;                // local sample i is sample g0 + i, clamped into [0, L)
+    const BmWaveNorm norm = bm_wave_norm(g.mom, blockIdx.y);
+    const long g0 = (long)f0 * g.old_ - g.width;                // local sample i is sample g0 + i, replicate-indexed
     const int nspan = (g.ft - 1) * g.old_ + g.ntp;
     const float* __restrict__ x = e.x;
     for (int i = threadIdx.x; i < nspan; i += RS_THREADS) {
-        long s = g0 + i;
-        s = s < 0 ? 0 : s > L - 1 ? L - 1 : s;
-        span[i] = g.mom ? (float)(((double)x[s] - shift) * scale) : x[s];
+        const long s = bm_wave_replicate(g0 + i, L);
+        span[i] = g.mom ? bm_wave_normed(x[s], norm) : x[s];
     }
     __syncthreads();
 }
 
 __global__ __launch_bounds__(RS_THREADS) void resample_mfma_kernel(const RsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float span[];
-    const RsWave e = g.table[blockIdx.y];
+    const BmWave e = g.table[blockIdx.y];
     const long out_len = (long)g.new_ * e.L / g.old_;
     const int f0 = blockIdx.x * g.ft;
     if ((long)f0 * g.new_ >= out_len) return;                   // uniform: a shorter waveform of the table
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_mfma_kernel(const RsArgs 
 
 __global__ __launch_bounds__(RS_THREADS) void resample_fma_kernel(const RsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float span[];
-    const RsWave e = g.table[blockIdx.y];
+    const BmWave e = g.table[blockIdx.y];
     const long out_len = (long)g.new_ * e.L / g.old_;
     const int f0 = blockIdx.x * g.ft;
     const long n0 = (long)f0 * g.new_;
@@ -139,19 +127,16 @@ extern "C" int bm_resample_frac(const void* table, const long* lengths, int n_wa
     const int ft = rs_frames_tile(old_rate, new_rate, width);
     BM_REQUIRE(ft > 0, "resample_frac: ratio %d / %d with width %d (new <= %d; 15 old + 2 width + old <= %d floats of LDS)",
                old_rate, new_rate, width, RS_MAX_NEW, RS_MAX_SPAN);
-    BM_REQUIRE(n_waves >= 0 && n_waves <= RS_MAX_WAVES, "resample_frac: %d waveforms, the limit is %d", n_waves, RS_MAX_WAVES);
-    if (n_waves == 0) return BM_OK;
-    BM_REQUIRE(table && lengths && taps, "resample_frac: null pointer");
+    const long tiles = bm_wave_tiles("resample_frac", table, lengths, n_waves, 0, "",
+                                     [=](long L) { return (L / old_rate + 1 + ft - 1) / ft; });
+    if (tiles <= 0) return (int)-tiles;                         // no waveform, or the error
+    for (int w = 0; w < n_waves; ++w)
+        BM_REQUIRE(new_rate * lengths[w] / old_rate < (1L << 31),
+                   "resample_frac: waveform %d has %ld samples (fewer than 2^31 outputs)", w, lengths[w]);
+    BM_REQUIRE(taps, "resample_frac: null pointer");
     BM_REQUIRE(((uintptr_t)mom & 7) == 0 && ((uintptr_t)taps & 3) == 0, "resample_frac: a table is not aligned");
-    long tiles = 0;
-    for (int w = 0; w < n_waves; ++w) {                         // lengths (HOST memory): the table's own, for the grid
-        BM_REQUIRE(lengths[w] >= 1 && lengths[w] < (1L << 31) && new_rate * lengths[w] / old_rate < (1L << 31),
-                   "resample_frac: waveform %d has %ld samples (1 <= L < 2^31, and as many outputs at most)", w, lengths[w]);
-        const long t = (lengths[w] / old_rate + 1 + ft - 1) / ft;
-        tiles = t > tiles ? t : tiles;
-    }
     RsArgs g;
-    g.table = (const RsWave*)table;
+    g.table = (const BmWave*)table;
     g.mom = mom;
     g.taps = taps;
     g.old_ = old_rate;

@@ -6,6 +6,7 @@ and enqueues the HIP kernels on the current stream.  CPU tensors are rejected --
 fallback path.
 """
 import ctypes
+import math
 import typing as tp
 
 import numpy as np
@@ -1775,7 +1776,7 @@ def segment_features(table: EventTable, rec: torch.Tensor, wstart: torch.Tensor,
 # a periodic Hann window of n_fft samples; "normalized" divides by sqrt(sum w^2); |.|^2; the htk filterbank of
 # melscale_fbanks with norm=None, f_min = 0, f_max = in_sampling // 2).
 MEL_FRAME_TILE = 32            # frames per workgroup for n_fft <= 1024 (``mel_frame_tile``: 16 beyond)
-MEL_MIN_NFFT, MEL_MAX_NFFT, MEL_MAX_MELS, MEL_MAX_WAVES = 8, 2048, 256, 65535
+MEL_MIN_NFFT, MEL_MAX_NFFT, MEL_MAX_MELS = 8, 2048, 256
 _mel_host_cache: tp.Dict[tp.Any, tp.Any] = {}
 _mel_device_cache: tp.Dict[tp.Any, tp.Any] = {}
 
@@ -1861,16 +1862,23 @@ def _mel_device_tables(n_fft, n_mels, in_sampling, normalized, device):
     return (basis, nbp) + fb
 
 
-def _wave_list(waves, what, min_len=0):
+# The wave table (csrc/bm_wave.h): what mel_spectrograms, resample_frac, yin_pitch and wave_moments share before they launch.
+WAVE_MAX_WAVES = 65535
+_wave_ticket_cache: tp.Dict[tp.Any, torch.Tensor] = {}
+
+
+def _wave_list(waves, what, wrong=lambda L: None):
+    """The waveforms as a checked list.  The limits come first -- they need no device: at most 65535 waveforms, each of
+    ``1 <= L < 2^31`` samples with nothing ``wrong(L)`` (the caller's own limit in words) -- then fp32, 1-D, one device."""
     waves = list(waves)
-    if len(waves) > MEL_MAX_WAVES:
-        raise ValueError(f"{what}: {len(waves)} waveforms in one call, the limit is {MEL_MAX_WAVES}")
-    for i, x in enumerate(waves):                               # the limits first: they do not need a device
-        if isinstance(x, torch.Tensor) and x.dim() == 1 and not 1 <= x.numel() < 2 ** 31:
-            raise ValueError(f"{what}: waveform {i} has {x.numel()} samples; the kernels take 1 <= L < 2^31")
-        if isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() <= min_len:
-            raise ValueError(f"{what}: waveform {i} has {x.numel()} samples; the reflect padding needs "
-                             f"L > n_fft // 2 = {min_len}")
+    if len(waves) > WAVE_MAX_WAVES:
+        raise ValueError(f"{what}: {len(waves)} waveforms in one call, the limit is {WAVE_MAX_WAVES}")
+    for i, x in enumerate(waves):
+        if isinstance(x, torch.Tensor) and x.dim() == 1:
+            L = x.numel()
+            why = wrong(L) if 1 <= L < 2 ** 31 else "the kernels take 1 <= L < 2^31"
+            if why is not None:
+                raise ValueError(f"{what}: waveform {i} has {L} samples; {why}")
     for i, x in enumerate(waves):
         _req(x, f"{what}: waveform {i}")
         if x.dim() != 1 or x.device != waves[0].device:
@@ -1879,29 +1887,35 @@ def _wave_list(waves, what, min_len=0):
     return waves
 
 
-def _wave_table(waves, outs):
-    """The device table of csrc/mel.hip (a host buffer and ONE copy: no launch) and the lengths on the host."""
-    L = lib()
-    host = torch.zeros(len(waves), L.bm_mel_table_entry_bytes(), dtype=torch.uint8)
+def _wave_batch(waves, what, out_shape=None, wrong=lambda L: None):
+    """``(waves, outs, table, lengths)`` of one launch over a wave table: the checked list (``_wave_list``); with
+    ``out_shape`` the fp32 output of shape ``out_shape(L)`` of every waveform, all carved from ONE allocation; the device
+    table (a host buffer and one copy: no launch); the lengths on the host.  No waveform: ``([], [], None, None)``."""
+    waves = _wave_list(waves, what, wrong)
+    if not waves:
+        return waves, [], None, None
+    L, device = lib(), waves[0].device
+    outs = []
+    if out_shape is not None:
+        shapes = [out_shape(x.numel()) for x in waves]
+        sizes = [math.prod(shape) for shape in shapes]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+        outs = [piece.view(shape) for piece, shape in zip(flat.split(sizes), shapes)]
+    entry = L.bm_wave_table_entry_bytes()
+    host = torch.zeros(len(waves), entry, dtype=torch.uint8)
     for i, x in enumerate(waves):
-        check(L.bm_mel_table_fill(ctypes.c_void_p(host[i].data_ptr()), _p(x), x.numel(), _p(outs[i]) if outs else None),
-              "bm_mel_table_fill")
-    return host.to(waves[0].device), np.ascontiguousarray([x.numel() for x in waves], dtype=np.int64)
-
-
-def _wave_tickets(n: int, device) -> torch.Tensor:
-    """``n`` zeroed ticket counters of this stream (every launch leaves them at zero again, csrc/bm_block.h)."""
-    key = ("tickets", device, torch.cuda.current_stream(device).cuda_stream)
-    t = _mel_device_cache.get(key)
-    if t is None or t.numel() < n:
-        t = _mel_device_cache[key] = torch.zeros(max(n, 1024), dtype=torch.int32, device=device)
-    return t
+        check(L.bm_wave_table_fill(host.data_ptr() + i * entry, _p(x), x.numel(), _p(outs[i]) if outs else None),
+              "bm_wave_table_fill")
+    return waves, outs, host.to(device), np.ascontiguousarray([x.numel() for x in waves], dtype=np.int64)
 
 
 def _wave_moments(table, lengths, device) -> torch.Tensor:
     n = len(lengths)
     max_splits = max(int(lib().bm_wave_moments_splits(int(v))) for v in lengths)
-    tickets = _wave_tickets(n, device)
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    tickets = _wave_ticket_cache.get(key)       # zeroed counters of this stream: a launch leaves them at zero (csrc/bm_block.h)
+    if tickets is None or tickets.numel() < n:
+        tickets = _wave_ticket_cache[key] = torch.zeros(max(n, 1024), dtype=torch.int32, device=device)
     part = torch.empty(n, max_splits, 2, dtype=torch.float64, device=device)
     mom = torch.empty(n, 2, dtype=torch.float64, device=device)
 
@@ -1922,10 +1936,9 @@ def _moments_arg(moments, n: int, device, what: str) -> torch.Tensor:
 def wave_moments(waves: tp.Sequence[torch.Tensor]) -> torch.Tensor:
     """``[n, 2]`` float64 on the device: ``(mean, 1 / (1e-8 + unbiased std))`` of every 1-D fp32 device waveform, in fp64,
     ONE launch for all of them and no host read-back -- the ``(shift, scale)`` of MelSpectrum's ``norm_audio``."""
-    waves = _wave_list(waves, "wave_moments")
+    waves, _, table, lengths = _wave_batch(waves, "wave_moments")
     if not waves:
         raise BmHipError("wave_moments: no waveform")
-    table, lengths = _wave_table(waves, None)
     return _wave_moments(table, lengths, waves[0].device)
 
 
@@ -1939,19 +1952,14 @@ def mel_spectrograms(waves: tp.Sequence[torch.Tensor], n_mels: int = 40, n_fft: 
     ``moments`` (``[n, 2]`` float64 on the device, ``(shift, scale)`` per waveform): used as they are instead of the
     statistics launch, whatever ``norm_audio`` says -- waveforms that were normalised before they were resampled."""
     mel_check_limits(n_fft, n_mels)
-    waves = _wave_list(waves, "mel_spectrograms", n_fft // 2)
+    hop = n_fft // 4
+    waves, outs, table, lengths = _wave_batch(
+        waves, "mel_spectrograms", out_shape=lambda L: (n_mels, 1 + L // hop),
+        wrong=lambda L: f"the reflect padding needs L > n_fft // 2 = {n_fft // 2}" if L <= n_fft // 2 else None)
     if not waves:
         return []
-    hop = n_fft // 4
     device = waves[0].device
     basis, nbp, fbw, rng, rng_host = _mel_device_tables(n_fft, n_mels, in_sampling, normalized, device)
-    frames = [1 + x.numel() // hop for x in waves]
-    flat = torch.empty(n_mels * sum(frames), dtype=torch.float32, device=device)
-    outs, at = [], 0
-    for f in frames:
-        outs.append(flat[at:at + n_mels * f].view(n_mels, f))
-        at += n_mels * f
-    table, lengths = _wave_table(waves, outs)
     if moments is not None:
         mom = _moments_arg(moments, len(waves), device, "mel_spectrograms")
     else:
@@ -1961,7 +1969,7 @@ def mel_spectrograms(waves: tp.Sequence[torch.Tensor], n_mels: int = 40, n_fft: 
         check(lib().bm_mel_spectrogram(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), _p(mom), _p(basis),
                                        n_fft, nbp, _p(fbw), _p(rng), ctypes.c_void_p(rng_host.ctypes.data), n_mels,
                                        int(bool(use_log_scale)), float(log_scale_eps), _stream()), "bm_mel_spectrogram")
-    _timed("mel_spectrogram", 4. * n_fft * nbp * sum(frames), launch)
+    _timed("mel_spectrogram", 4. * n_fft * nbp * sum(o.shape[1] for o in outs), launch)
     return outs
 
 
@@ -1974,7 +1982,6 @@ _resample_taps: tp.Dict[tp.Any, tp.Any] = {}
 
 def resample_ratio(old_sr: int, new_sr: int) -> tp.Tuple[int, int]:
     """``(old, new)``: the two rates divided by their gcd.  Integer rates of at least 1 Hz, else ``ValueError``."""
-    import math
     for name, sr in (("old_sr", old_sr), ("new_sr", new_sr)):
         if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr < 1:
             raise ValueError(f"resample: {name} = {sr!r}; the rates are integers of at least 1 Hz")
@@ -1999,7 +2006,6 @@ def resample_taps(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.
     the first element is the kernel's table instead: ``[ntaps to a multiple of 4, new to a multiple of 16]`` on that
     device, tap-major, zero-padded.  Cached per (old, new, zeros, rolloff, device).  ``old == new``: ``ValueError`` (the
     identity has no filter)."""
-    import math
     old, new = resample_ratio(old_sr, new_sr)
     if old == new:
         raise ValueError(f"resample: {old_sr} Hz -> {new_sr} Hz is the identity; it has no filter")
@@ -2061,34 +2067,25 @@ def resample_frac(waves: tp.Sequence[torch.Tensor], old_sr: int, new_sr: int, ze
     -- the reference normalises at the source rate.  Limits (``ValueError`` before any launch): ``new <= 4096`` phases,
     ``15 * old + ntaps <= 16384`` staged samples, ``L < 2^31`` in and out, 65535 waveforms."""
     old, new = resample_ratio(old_sr, new_sr)
-    waves = list(waves)
     if old == new:
         if moments is not None:
             raise ValueError("resample_frac: equal rates return the waveforms as they are; moments cannot be applied")
         return _wave_list(waves, "resample_frac")
     _, _, _, width = resample_taps(old_sr, new_sr, zeros, rolloff)              # the limits first: they need no device
-    for i, x in enumerate(waves):
-        if isinstance(x, torch.Tensor) and x.dim() == 1 and resample_length(x.numel(), old, new) >= 2 ** 31:
-            raise ValueError(f"resample_frac: waveform {i} of {x.numel()} samples gives "
-                             f"{resample_length(x.numel(), old, new)} outputs; the kernel takes fewer than 2^31")
-    waves = _wave_list(waves, "resample_frac")
+    waves, outs, table, lengths = _wave_batch(
+        waves, "resample_frac", out_shape=lambda L: (resample_length(L, old, new),),
+        wrong=lambda L: (f"they give {resample_length(L, old, new)} outputs, the kernel takes fewer than 2^31"
+                         if resample_length(L, old, new) >= 2 ** 31 else None))
     if not waves:
         return []
     device = waves[0].device
     taps = resample_taps(old_sr, new_sr, zeros, rolloff, device)[0]
     mom = _moments_arg(moments, len(waves), device, "resample_frac") if moments is not None else None
-    lens = [resample_length(x.numel(), old, new) for x in waves]
-    flat = torch.empty(sum(lens), dtype=torch.float32, device=device)
-    outs, at = [], 0
-    for n in lens:
-        outs.append(flat[at:at + n])
-        at += n
-    table, lengths = _wave_table(waves, outs)
 
     def launch():
         check(lib().bm_resample_frac(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), _p(mom), _p(taps), old,
                                      new, width, _stream()), "bm_resample_frac")
-    _timed("resample_frac", 2. * (2 * width + old) * sum(lens), launch)
+    _timed("resample_frac", 2. * (2 * width + old) * sum(o.numel() for o in outs), launch)
     return outs
 
 
@@ -2124,24 +2121,14 @@ def yin_pitch(waves: tp.Sequence[torch.Tensor], sr: float = 16_000, w_len: int =
     under the threshold walked to its bottom, ``sr / tau``; 0.0 for an unvoiced, a silent or a non-finite frame.
     ``ValueError``: ``L <= w_len``, ``tau_max > w_len``, ``tau_min < 1``, ``w_len > 1024``, ``w_step > 512``."""
     tau_min, tau_max = yin_taus(sr, w_len, w_step, f0_min, f0_max)
-    waves = list(waves)
-    for i, x in enumerate(waves):                               # the limits first: they need no device
-        if isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() <= w_len:
-            raise ValueError(f"yin_pitch: waveform {i} has {x.numel()} samples; a frame needs L > w_len = {w_len}")
-    waves = _wave_list(waves, "yin_pitch")
+    waves, outs, table, lengths = _wave_batch(
+        waves, "yin_pitch", out_shape=lambda L: (1, yin_frames(L, w_len, w_step)),
+        wrong=lambda L: f"a frame needs L > w_len = {w_len}" if L <= w_len else None)
     if not waves:
         return []
-    device = waves[0].device
-    frames = [yin_frames(x.numel(), w_len, w_step) for x in waves]
-    flat = torch.empty(sum(frames), dtype=torch.float32, device=device)
-    outs, at = [], 0
-    for f in frames:
-        outs.append(flat[at:at + f].view(1, f))
-        at += f
-    table, lengths = _wave_table(waves, outs)
 
     def launch():
         check(lib().bm_yin_pitch(_p(table), ctypes.c_void_p(lengths.ctypes.data), len(waves), float(sr), w_len, w_step,
                                  tau_min, tau_max, float(harmo_thresh), _stream()), "bm_yin_pitch")
-    _timed("yin_pitch", 3. * w_len * tau_max * sum(frames), launch)
+    _timed("yin_pitch", 3. * w_len * tau_max * sum(o.shape[1] for o in outs), launch)
     return outs

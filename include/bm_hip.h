@@ -472,14 +472,20 @@ int bm_segment_features(const int* feat_table, const float* feat_default, int NF
                         const double* wdur, long n_index, long first, int B, int F, int T, double sr, float* dst,
                         unsigned char* mask, int* flag, void* stream);
 
+/* ---- the wave table of the three audio units below (csrc/bm_wave.h) ----
+ * table: n_waves <= 65535 entries of bm_wave_table_entry_bytes bytes on the device, each filled on the host by
+ * bm_wave_table_fill: {x: a 1-D fp32 waveform on the device, read in place; out: where the unit stores that waveform's
+ * result (null for bm_wave_moments), both 4-byte aligned; L: its length, 1 <= L < 2^31}.  lengths (HOST memory): the same
+ * lengths, for the grid and the checks. */
+long bm_wave_table_entry_bytes(void);
+int bm_wave_table_fill(void* entry, const float* x, long L, float* out);
+
 /* ---- the MelSpectrum targets from resident waveforms (mel.hip)  bm/features/audio.py:61-76 ----
  * MelSpectrum._compute behind the channel mean: (wav - wav.mean()) / (1e-8 + wav.std()) (unbiased std), then
  * torchaudio.transforms.MelSpectrogram(n_fft, hop = n_fft / 4, normalized) RESTATED from its documentation -- torch.stft
  * with center=True, reflect padding, a periodic Hann window of n_fft samples, divided by sqrt(sum w^2) when normalized,
  * |.|^2, times the htk filterbank -- and log10(mel + eps).  Two launches for any number of waveforms.
- * table: n_waves entries (bm_mel_table_entry_bytes bytes each, filled on the host by bm_mel_table_fill) {address of a 1-D
- * fp32 waveform on the device, read in place, 4-byte aligned; its length, 1 <= L < 2^31; address of its [n_mels][1 + L /
- * hop] output (null for bm_wave_moments)}.  lengths (HOST memory): the same lengths, for the grid and the checks.
+ * table, lengths: the wave table, `out` the [n_mels][1 + L / hop] output of the waveform.
  * bm_wave_moments: mom[w] = {mean, 1 / (1e-8 + unbiased std)} in fp64, ONE launch over a (split, waveform) grid: a
  * waveform is cut into bm_wave_moments_splits(L) splits (a function of L alone), every split is walked twice (its sum,
  * then its squares centred on its own mean) and the workgroup of a waveform that finishes last folds the partials in
@@ -494,8 +500,6 @@ int bm_segment_features(const int* feat_table, const float* feat_default, int NF
  * tile, the grid or the other waveforms.  fbw: [n_mels][n_fft / 2 + 1] filter weights; range (device) and range_host (HOST, the same values):
  * [n_mels][2] = the bins [lo, hi) that row m sums, ascending, by fmaf from 0.f.  8 <= n_fft <= 2048, n_fft % 4 == 0,
  * n_mels <= 256, n_fft / 2 < L, n_waves <= 65535. */
-long bm_mel_table_entry_bytes(void);
-int bm_mel_table_fill(void* entry, const float* x, long L, float* out);
 int bm_mel_frame_tile(int n_fft);
 int bm_wave_moments_splits(long L);
 int bm_wave_moments(const void* table, const long* lengths, int n_waves, unsigned* tickets, double* part,
@@ -509,8 +513,8 @@ int bm_mel_spectrogram(const void* table, const long* lengths, int n_waves, cons
  * every waveform of one reduced ratio old_rate / new_rate (already divided by their gcd, old_rate != new_rate):
  *     out[f new + i] = sum_k taps[i][k] padded[f old + k],  k < ntaps = 2 width + old,  f new + i < floor(new L / old),
  * `padded` the waveform replicate-padded by width samples on the left and width + old on the right (indexed in place: no
- * padded copy).  table: mel.hip's entries (bm_mel_table_fill), `out` the floor(new L / old) outputs of the waveform;
- * lengths (HOST memory): the same lengths.  mom: null, or what bm_wave_moments wrote for the same table: a sample
+ * padded copy).  table, lengths: the wave table, `out` the floor(new L / old) outputs of the waveform.
+ * mom: null, or what bm_wave_moments wrote for the same table: a sample
  * enters as (float)(((double)x - shift) * scale).  taps: [ntp][newp] fp32, taps[k][i] the tap k of phase i, ntp = ntaps
  * rounded up to 4 and newp = new rounded up to 16, zero beyond ntaps and beyond new.  Grid (tile of
  * bm_resample_frames_tile frames, waveform); the samples a tile covers are staged in LDS once.  new >= 16:
@@ -529,7 +533,7 @@ int bm_resample_frac(const void* table, const long* lengths, int n_waves, const 
  * reference's FFT expression as a sum);  c(0) = 0, c(tau) = d(tau) tau / sum_{1..tau} d  with the running sum in
  * ascending tau;  the first tau in [tau_min, tau_max) with c < thresh, walked down while c(tau + 1) < c(tau) and tau + 1 <
  * tau_max;  out[t] = (float)(sr / tau), or 0.f when there is none.  A silent frame (0 / 0) and a frame holding a NaN or
- * an Inf give 0.f.  table: mel.hip's entries, `out` the waveform's frames; lengths (HOST memory).  Grid (tile of
+ * an Inf give 0.f.  table, lengths: the wave table, `out` the waveform's frames.  Grid (tile of
  * bm_yin_frames_tile frames, waveform), one wavefront per frame, samples staged in LDS once; no atomics.
  * Limits (BM_ERR_ARG): w_len < L < 2^31, 2 <= w_len <= 1024, 1 <= w_step <= 512, 1 <= tau_min, tau_max <= w_len,
  * n_waves <= 65535. */

@@ -190,7 +190,7 @@ def test_library_declares_the_mel_entry_points():
     from brainmagick_amd import _lib
     L = _lib.lib()
     assert L.bm_version() >= 114
-    assert {"bm_wave_moments", "bm_mel_spectrogram", "bm_mel_table_fill"} <= set(_lib.parse_header())
+    assert {"bm_wave_moments", "bm_mel_spectrogram", "bm_wave_table_fill"} <= set(_lib.parse_header())
     from brainmagick_amd import hip_ops as H
     assert H.mel_frame_tile(512) == H.MEL_FRAME_TILE and H.mel_frame_tile(2048) == 16
     assert L.bm_wave_moments_splits(9) == 1 and L.bm_wave_moments_splits(70001) == 5
