@@ -20,7 +20,7 @@ int bm_check_launch(const char* what) {
 }
 
 extern "C" const char* bm_last_error(void) { return bm_err_buf; }
-extern "C" int bm_version(void) { return 116; }   // 0.1.16: one wave table for the audio units (bm_wave_table_fill, was bm_mel_table_fill)
+extern "C" int bm_version(void) { return 117; }   // 0.1.17: bm_fir_rows, the long FIR of the MEG preprocessing
 
 // Number of HIP devices visible; <0 on error.  Lets the Python side fail loudly early.
 extern "C" int bm_device_count(void) {

@@ -12,6 +12,8 @@ sample)`` arrays of the epoch, which are uploaded once per epoch.
   mne's documentation (mne itself cannot be run against this).
 - ``DeviceRecording``, ``DeviceSegments``, ``DeviceSegmentLoader``: the dataset and its loader; torch's own samplers
   decide the order, the loader only replaces what they index.
+- ``preprocess_meg`` / ``DeviceRecording.from_raw``: the resampling and the ``highpass`` of ``preprocess_mne``
+  (bm/studies/api.py:334-363) over the raw recording, one launch each (csrc/resample.hip, csrc/fir.hip).
 
 The features of a batch come either from full-length arrays (two more gathers) or from the recording's events
 (``DeviceRecording(meg, events=features.DeviceEvents(...))``): then ONE ``hip_ops.segment_features`` launch builds the
@@ -19,7 +21,8 @@ features and the mask of the batch by the reference's per-window rules (features
 
 Not built: WordPulse / PhonemePulse (``post_process``), Wav2VecChunk, the batch's ``_event_lists``, computing the
 wav2vec2 states / embeddings themselves (the mel spectrogram and the pitch: ``audio.py``), ``autoreject``,
-``split_wav_as_block``, ``decim != 1``, channel picking, resampling / ``highpass`` of the MEG.  There is no CPU fallback.
+``split_wav_as_block``, ``decim != 1``, channel picking, reading ``.fif`` files, ``mne.Info`` and layouts.  There is no CPU
+fallback.
 """
 import copy
 import typing as tp
@@ -127,8 +130,39 @@ def raise_if_range_error(device) -> None:
         raise IndexError("a segment's recording or first sample is out of range (such segments were gathered as zeros)")
 
 
+def preprocess_meg(raw, sfreq: float, sample_rate, highpass: float = 0.) -> torch.Tensor:
+    """``preprocess_mne(raw, sample_rate, highpass).get_data()`` (bm/studies/api.py:334-363) under the rate rules of
+    ``Recording.preprocessed`` (bm/studies/api.py:208-216), on the device: ``raw`` [C, L] (the raw recording's
+    ``get_data()`` at ``sfreq`` Hz; a tensor or an array, moved to the GPU as fp32) -> [C, floor(new L / old)] fp32.
+    ``old_sr = int(np.round(sfreq))``; julius' ``ResampleFrac(old_sr, sample_rate)`` over the channels (ONE launch,
+    ``hip_ops.resample_rows``), then, with ``highpass``, ``data -= lowpass_filter(data, highpass / sample_rate)`` (ONE
+    launch, ``hip_ops.highpass_filter``; ``zeros = 8``, a Python float division as in the reference: ``int()`` of it
+    decides the filter's length).  ``sample_rate == old_sr`` without ``highpass`` hands the tensor through untouched
+    and launches nothing (the reference's ``(0, 0.0)`` key: the raw recording itself).  julius is restated, see
+    ``hip_ops.resample_taps`` / ``lowpass_taps``; reading the file, ``mne.Info`` and layouts are not built."""
+    if sample_rate != int(sample_rate):
+        raise ValueError("For simplicity's sake, only integer sampling rates in Hz are allowed")
+    sample_rate = int(sample_rate)
+    old_sr = int(np.round(sfreq))
+    if sample_rate > old_sr:
+        raise ValueError(f"The sample rate should be below {old_sr}Hz, got {sample_rate}")
+    if highpass:
+        H._check_cutoff(highpass / sample_rate)                    # julius' errors, before anything is uploaded
+    data = torch.as_tensor(raw)
+    if data.dim() != 2:
+        raise ValueError(f"expected [channels, samples], got {tuple(data.shape)}")
+    if not (data.is_cuda and data.dtype == torch.float32):
+        if not torch.cuda.is_available():
+            raise BmHipError("preprocess_meg: no GPU; the brainmagick_amd hot path has no CPU fallback")
+        data = data.to(device="cuda", dtype=torch.float32)
+    data = H.resample_rows(data, old_sr, sample_rate)
+    if highpass:
+        data = H.highpass_filter(data, highpass / sample_rate)
+    return data
+
+
 class DeviceRecording:
-    """One preprocessed recording on the device.  ``meg``: [C_r, N] fp32, ``features``: [F, N] fp32, ``features_mask``:
+    """One preprocessed recording on the device. ``meg``: [C_r, N] fp32, ``features``: [F, N] fp32, ``features_mask``:
     [M, N] bool; a tensor that is already there is adopted without a copy.  ``events`` (``features.DeviceEvents``)
     instead of ``features`` / ``features_mask``: the features and the mask of a batch are built from the events by
     ``hip_ops.segment_features``.  ``recording``: anything with ``recording_index`` and ``layout``
@@ -155,6 +189,12 @@ class DeviceRecording:
             t = getattr(self, name)
             if t is not None and t.shape[1] != self.n_samples:
                 raise ValueError(f"{name} has {t.shape[1]} samples, the MEG has {self.n_samples}")
+
+    @classmethod
+    def from_raw(cls, raw, sfreq: float, sample_rate, highpass: float = 0., **kw) -> "DeviceRecording":
+        """The recording from its RAW MEG ``[C, L]`` at ``sfreq`` Hz: ``preprocess_meg`` on the device, then the
+        constructor with ``kw`` as it is (features and events are at ``sample_rate``)."""
+        return cls(preprocess_meg(raw, sfreq, sample_rate, highpass), **kw)
 
     @staticmethod
     def _adopt(t, dtype, device) -> torch.Tensor:

@@ -1136,6 +1136,84 @@ def lowpass_filter(x: torch.Tensor, cutoff: float, stride: int = 1, pad: bool = 
     return y
 
 
+# The long FIR of the MEG preprocessing (csrc/fir.hip; bm/studies/api.py:334-363): rows tiled in time, taps walked in chunks.
+FIR_MAX_HALF, FIR_MAX_ROWS = 16384, 65535
+
+
+def fir_tile() -> int:
+    """Consecutive outputs of one row that a workgroup of ``bm_fir_rows`` owns."""
+    return int(lib().bm_fir_tile())
+
+
+def fir_chunk() -> int:
+    """Values of ``j = tap + column`` (``ntaps + 15`` in all) that ``bm_fir_rows`` stages at a time."""
+    return int(lib().bm_fir_chunk())
+
+
+def fir_rows(x: torch.Tensor, taps: torch.Tensor, subtract: bool = False) -> torch.Tensor:
+    """``s[..., t] = sum_k taps[k] * x[..., clamp(t + k - half, 0, T - 1)]`` over the last dimension, ``half = (ntaps - 1)
+    / 2`` -- ``lowpass_filter``'s replicate padding without its limit on ``T + 2 half`` -- and ``x - s`` with
+    ``subtract``: ONE launch of ``bm_fir_rows``, a new contiguous tensor of ``x.shape``.  ``x``: fp32 on the GPU, any
+    leading dimensions; a view whose rows are uniformly strided is read in place, anything else is made contiguous
+    first.  ``taps``: 1-D fp32 on the same device, of odd length.
+
+    The sum is the exact-fp32 MFMA's fmaf chain, taps ascending from 0.f, whatever the compute mode: an output's bits
+    depend on its own window alone, and for finite ``x`` the outputs equal ``lowpass_filter``'s as numbers wherever
+    that applies.  A non-finite sample makes non-finite every output within ``half`` of it, may do so up to 15 samples
+    further, and nothing beyond.  Limits (``ValueError`` before any launch): ``1 <= T < 2^31``, at most 65535 rows,
+    ``ntaps`` odd, ``half <= 16384``."""
+    if not isinstance(taps, torch.Tensor) or taps.dim() != 1 or taps.numel() % 2 != 1:
+        raise ValueError(f"fir_rows: taps of shape {tuple(getattr(taps, 'shape', ()))}; a 1-D tensor of odd length "
+                         "(2 half + 1)")
+    half = (taps.numel() - 1) // 2
+    if half > FIR_MAX_HALF:
+        raise ValueError(f"fir_rows: half = {half}; the kernel takes half <= {FIR_MAX_HALF}")
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise ValueError("fir_rows: x has no last dimension")
+    T = x.shape[-1]
+    if not 1 <= T < 2 ** 31:
+        raise ValueError(f"fir_rows: rows of {T} samples; the kernel takes 1 <= T < 2^31")
+    rows = x.numel() // T
+    if rows > FIR_MAX_ROWS:
+        raise ValueError(f"fir_rows: {rows} rows in one call, the limit is {FIR_MAX_ROWS}")
+    _req(x, "fir_rows.x", contiguous=False)
+    _req(taps, "fir_rows.taps")
+    if taps.device != x.device:
+        raise BmHipError(f"fir_rows: taps on {taps.device}, x on {x.device}")
+    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    if rows == 0:
+        return y
+    row_stride = _uniform_rows(x)
+    if row_stride is None:
+        x, row_stride = x.contiguous(), T
+
+    def launch():
+        check(lib().bm_fir_rows(_p(x), row_stride, _p(y), rows, T, _p(taps), taps.numel(), int(bool(subtract)),
+                                _stream()), "bm_fir_rows")
+    _timed("fir_rows", 2. * taps.numel() * rows * T, launch)
+    return y
+
+
+def highpass_filter(x: torch.Tensor, cutoff: float, stride: int = 1, pad: bool = True, zeros: float = 8,
+                    fft: tp.Optional[bool] = None) -> torch.Tensor:
+    """``julius.highpass_filter(x, cutoff, stride, pad, zeros, fft)`` over the last dimension: ``x - lowpass(x)``, what
+    ``julius.HighPassFilter`` computes, as ``lowpass_taps(cutoff, zeros)`` and ONE ``bm_fir_rows`` launch that
+    subtracts in its epilogue.  ``x`` as for ``fir_rows``.  Always the direct sum (``fft`` is accepted and ignored);
+    ``stride != 1`` and ``pad=False`` are not built."""
+    if stride != 1:
+        raise NotImplementedError("highpass_filter: stride != 1 (julius' decimating form) is not built")
+    if not pad:
+        raise NotImplementedError("highpass_filter: pad=False (julius' valid convolution) is not built")
+    _check_cutoff(cutoff)
+    half = int(zeros / cutoff / 2)
+    if half > FIR_MAX_HALF:
+        raise ValueError(f"highpass_filter: cutoff {cutoff} with zeros = {zeros} is half = {half}; the kernel takes "
+                         f"half <= {FIR_MAX_HALF}")
+    device = x.device if isinstance(x, torch.Tensor) else None
+    taps, _ = lowpass_taps(cutoff, zeros, device)
+    return fir_rows(x, taps, subtract=True)
+
+
 # FeatureDecodingLoss / ClassificationAcc (csrc/regress.hip). ``table``: one row per feature, (kind, est_start, width,
 # out_start, weight_off) with kind 0 = continuous, 1 = categorical (width = number of classes) and weight_off the
 # feature's offset into ``weights`` or -1.
@@ -2087,6 +2165,27 @@ def resample_frac(waves: tp.Sequence[torch.Tensor], old_sr: int, new_sr: int, ze
                                      new, width, _stream()), "bm_resample_frac")
     _timed("resample_frac", 2. * (2 * width + old) * sum(o.numel() for o in outs), launch)
     return outs
+
+
+def resample_rows(x: torch.Tensor, old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945) -> torch.Tensor:
+    """``julius.resample.ResampleFrac(old_sr, new_sr, zeros, rolloff)(x)`` for a ``[C, L]`` fp32 device tensor (the
+    channels of a recording): a contiguous ``[C, floor(new * L / old)]``.  The rows are the waveforms of ONE
+    ``resample_frac`` launch (rows of unit stride are read in place, whatever lies between them), whose outputs, carved
+    from one allocation, are the result: the same bits as ``resample_frac`` over the rows, the same limits.  Equal rates
+    return ``x`` itself, as julius does."""
+    old, new = resample_ratio(old_sr, new_sr)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"resample_rows: expected [channels, samples], got {tuple(getattr(x, 'shape', ()))}")
+    if old == new:
+        return x
+    C, L = x.shape
+    if C and L != 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    n = resample_length(L, old, new)
+    outs = resample_frac(list(x.unbind(0)), old_sr, new_sr, zeros, rolloff)
+    if not outs:
+        return torch.empty(0, n, dtype=torch.float32, device=x.device)
+    return outs[0].as_strided((C, n), (n, 1))                   # the one allocation behind the outputs
 
 
 # The Pitch feature (csrc/pitch.hip; bm/features/audio.py:110-124, bm/lib/pitch_calc/yin.py).

@@ -527,6 +527,27 @@ int bm_resample_frames_tile(int old_rate, int new_rate, int width);
 int bm_resample_frac(const void* table, const long* lengths, int n_waves, const double* mom, const float* taps,
                      int old_rate, int new_rate, int width, void* stream);
 
+/* ---- a long FIR over long rows (fir.hip)  bm/studies/api.py:334-363 (preprocess_mne's highpass) ----
+ * With half = (ntaps - 1) / 2, ONE launch:
+ *     s[r][t] = sum_{k < ntaps} taps[k] * x[r][clamp(t + k - half, 0, T - 1)],   y[r][t] = subtract ? x[r][t] - s : s
+ * -- bm_lowpass's replicate padding, but rows are tiled in time and the taps are walked in chunks, so neither T nor half
+ * is bounded by LDS.  x: `rows` rows of T fp32 samples, unit stride inside a row, row_stride >= T floats between rows (a
+ * view is read in place); nothing outside [row start, row start + T) is read.  y: contiguous [rows][T], every element
+ * stored exactly once, no atomics.  taps: ntaps floats on the device.  Grid (tile of bm_fir_tile outputs, row); the tap
+ * axis is walked in chunks of bm_fir_chunk values of j = tap + column, j in [0, ntaps + 15).
+ * Arithmetic: v_mfma_f32_16x16x4_f32 in every compute mode, the Toeplitz form of the resampler, ONE accumulator chain per
+ * output with j ascending from 0.f carried across the chunks: an output's bits depend on its own window alone (not on
+ * the tile, the grid, the chunking or the other rows), and for finite input the outputs equal bm_lowpass's as numbers
+ * wherever that kernel applies.  A non-finite sample makes non-finite every output within `half` of it, may do so up to
+ * 15 samples further (0 * NaN in the zero corners of the Toeplitz operand), and nothing beyond.
+ * Limits (BM_ERR_ARG): 1 <= T < 2^31, rows <= 65535, ntaps odd, half <= bm_fir_max_half (16384); pointers 4-byte
+ * aligned; row offsets are 64-bit (rows * T is not limited).  rows == 0 returns without a launch. */
+int bm_fir_tile(void);
+int bm_fir_chunk(void);
+int bm_fir_max_half(void);
+int bm_fir_rows(const float* x, long row_stride, float* y, int rows, long T, const float* taps, int ntaps, int subtract,
+                void* stream);
+
 /* ---- the Pitch feature from resident waveforms (pitch.hip)  bm/features/audio.py:110-124, bm/lib/pitch_calc/yin.py ----
  * compute_yin(sig, sr, w_len, w_step, f0_min, f0_max, harmo_thresh)[0] as ONE launch: frame t < ceil((L - w_len) /
  * w_step) starts at t w_step;  d(tau) = sum_{j < w_len - tau} (x_j - x_{j + tau})^2  in fp64 with j ascending (the
