@@ -363,10 +363,15 @@ class DeviceSegments:
     def only(self, recording: int) -> "DeviceSegments":
         """The segments of one recording (its position in ``recordings``) over the same resident recordings and the
         same device tables."""
+        return self.subset([recording])
+
+    def subset(self, recordings: tp.Iterable[int]) -> "DeviceSegments":
+        """The segments of some recordings (their positions in ``recordings``), in this dataset's order, over the same
+        resident recordings and the same device tables."""
         if self.device.type == "cuda":
             self.tables()                                   # built once here, shared by every copy
         sub = copy.copy(self)
-        keep = self.rec == recording
+        keep = np.isin(self.rec, np.asarray(list(recordings), dtype=np.int64))
         sub.rec, sub.start = self.rec[keep], self.start[keep]
         if self.builder is not None:
             sub.wstart, sub.wdur = self.wstart[keep], self.wdur[keep]

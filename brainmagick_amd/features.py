@@ -107,6 +107,26 @@ class DeviceFeaturesBuilder(collections.OrderedDict):
         except KeyError:
             raise KeyError(f"no feature {name!r} among {list(self)}") from None
 
+    def extract_features(self, features: torch.Tensor, feature_names: tp.Sequence[str]) -> torch.Tensor:
+        """bm/features/base.py:145-160: the channels of ``feature_names``, in that order, out of a tensor ``[B,
+        dimension, T]`` that holds all of the builder's features.  Names that are the builder's first features in the
+        builder's order (the used features in front of the extra test features, bm/wer.py:49-50) are ONE leading run of
+        channels: a view, made contiguous once; anything else is one ``torch.cat`` of the slices, as the reference
+        writes it.  The result never shares memory with ``features`` unless it is all of it."""
+        assert features.shape[1] == self.dimension, "Input should contain all features"
+        feature_names = list(feature_names)
+        assert all([name in self for name in feature_names])
+        slices = [self.get_slice(name) for name in feature_names]
+        at = 0
+        for s in slices:
+            if s.start != at:
+                break
+            at = s.stop
+        else:
+            if slices:
+                return features[:, :at].contiguous()
+        return torch.cat([features[:, s] for s in slices], dim=1)
+
     @property
     def dimension(self) -> int:
         return self._widths[0]

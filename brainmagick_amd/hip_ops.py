@@ -2231,3 +2231,60 @@ def yin_pitch(waves: tp.Sequence[torch.Tensor], sr: float = 16_000, w_len: int =
                                  tau_min, tau_max, float(harmo_thresh), _stream()), "bm_yin_pitch")
     _timed("yin_pitch", 3. * w_len * tau_max * sum(o.shape[1] for o in outs), launch)
     return outs
+
+
+# The word label of every kept test segment (csrc/wer.hip, bm/wer.py:48, 58-66).
+WORD_HASH_ALL_ZERO_BIT = 1      # every candidate of a kept row is zero: the assert of bm/wer.py:65
+WORD_HASH_VALUE_BIT = 2         # the chosen value is not finite, not an integer, or |v| >= 2^63
+WORD_HASH_DEST_BIT = 4          # a kept row had no element of dest left
+
+
+def word_hash_pick_check(shape: tp.Sequence[int], c: int, check_at_time: int, n_dest: int, n0: int = 0,
+                         count: tp.Optional[int] = None) -> None:
+    """The ``ValueError``s of ``word_hash_pick``, from the shapes alone (nothing is launched, no tensor is touched):
+    features that are not ``[B, F_all, T]``; ``check_at_time < 0`` or ``check_at_time + 2 >= T`` (the reference's
+    ``word_hash[:, check_at_time + 2]`` would wrap around or raise ``IndexError``); ``c`` outside ``[0, F_all)``; a
+    negative ``n0``; a ``dest`` with fewer than ``n0 + count`` elements (``count``: the kept rows when the caller knows
+    them, else all ``B``)."""
+    if len(shape) != 3:
+        raise ValueError(f"word_hash_pick: the features are {tuple(shape)}, expected [B, F_all, T]")
+    B, F, T = (int(s) for s in shape)
+    if check_at_time < 0 or check_at_time + 2 >= T:
+        raise ValueError(f"word_hash_pick: check_at_time = {check_at_time} reads the samples {check_at_time - 2} .. "
+                         f"{check_at_time + 2} of a window of {T} (bm/wer.py:58-64 would wrap around or raise IndexError)")
+    if not 0 <= c < F:
+        raise ValueError(f"word_hash_pick: channel {c} of {F}")
+    count = B if count is None else int(count)
+    if not 0 <= count <= B:
+        raise ValueError(f"word_hash_pick: {count} kept rows of a batch of {B}")
+    if n0 < 0 or n0 + count > n_dest:
+        raise ValueError(f"word_hash_pick: dest holds {n_dest} labels, the batch writes {n0} .. {n0 + count - 1}")
+
+
+def word_hash_pick(features: torch.Tensor, c: int, check_at_time: int, reject_mask: tp.Optional[torch.Tensor],
+                   dest: torch.Tensor, n0: int, flag: torch.Tensor, count: tp.Optional[int] = None) -> None:
+    """``dest[n0 + r]`` = the word label of the kept row of rank ``r`` of the batch's full ``features`` ``[B, F_all, T]``
+    (fp32, contiguous, read in place): the first non-zero of channel ``c`` at ``check_at_time``, ``- 1`` (only if
+    ``check_at_time > 0``), ``+ 1``, ``- 2`` (only if ``> 1``), ``+ 2``, as the exact int64 of the fp32 value -- the
+    ``torch.where`` chain of bm/wer.py:58-64 over ``word_hash[reject_mask]``, ONE launch (``bm_word_hash_pick``).
+    ``reject_mask``: bool ``[B]`` (true = kept) or None (all kept); ``dest``: int64, contiguous; ``flag``: one int32 on
+    the device, see the ``WORD_HASH_*_BIT``s; ``count``: the number of kept rows when the caller knows it (it only
+    tightens the length check of ``dest``).  ``ValueError``s: ``word_hash_pick_check``, before any launch."""
+    if not isinstance(features, torch.Tensor) or not isinstance(dest, torch.Tensor):
+        raise BmHipError("word_hash_pick: features and dest are tensors")
+    word_hash_pick_check(features.shape, c, check_at_time, dest.numel(), n0, count)
+    _req(features, "word_hash_pick.features")
+    _req(dest, "word_hash_pick.dest", torch.int64)
+    _req(flag, "word_hash_pick.flag", torch.int32)
+    B, F, T = features.shape
+    if reject_mask is not None:
+        _req(reject_mask, "word_hash_pick.reject_mask", torch.bool)
+        if reject_mask.shape != (B,):
+            raise ValueError(f"word_hash_pick: reject_mask is {tuple(reject_mask.shape)} for a batch of {B}")
+    if dest.dim() != 1 or flag.numel() < 1:
+        raise ValueError("word_hash_pick: dest is one-dimensional and the flag holds one word")
+
+    def launch():
+        check(lib().bm_word_hash_pick(_p(features), B, F, T, int(c), int(check_at_time), _p(reject_mask), _p(dest),
+                                      dest.numel(), int(n0), _p(flag), _stream()), "bm_word_hash_pick")
+    _timed("word_hash_pick", 0., launch)

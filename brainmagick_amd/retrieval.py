@@ -7,11 +7,18 @@ its own label is among the labels of its top-k candidates).  Differences to the 
 candidate norms are computed once (not once per batch of predictions), probabilities stay on the
 GPU, and top-k + label matching are one HIP kernel (``bm_topk_rows``) instead of
 ``topk`` + gather + compare.
+
+``wer_epoch`` is the test epoch of a ClipLoss model, bm/wer.py:21-121 (``get_wer(solver)``): it collects the estimates,
+the outputs and the word label of every kept segment of a ``dataset.DeviceSegments`` test set in resident device arrays
+(bm/wer.py:24-69; the labels by ONE ``hip_ops.word_hash_pick`` launch per batch) and hands them to ``get_wer``
+(bm/wer.py:71-121).  Not built: a process group of more than one rank, a host-memory spill of the two arrays, and the
+soft WER, which the reference computes and never returns.
 """
 import typing as tp
 
 import torch
 
+from . import distrib
 from . import hip_ops as H
 from .losses import ClipLoss
 
@@ -64,7 +71,7 @@ def segment_topk_accuracy(clip: ClipLoss, preds: torch.Tensor, trues: torch.Tens
 def get_wer(clip: ClipLoss, estimates: torch.Tensor, outputs: torch.Tensor, word_hashes: torch.Tensor,
             n_negatives: tp.Optional[int] = 10_000, topx: int = 10,
             generator: tp.Optional[torch.Generator] = None,
-            batch_size: int = 1000) -> tp.Dict[str, float]:
+            batch_size: int = 1000, wer_random: bool = False) -> tp.Dict[str, float]:
     """Word-level top-k "word error rate" of bm/wer.py:67-121, batched on the GPU.
 
     Reference semantics, per test segment i: the negatives are a fixed random subset of the test
@@ -73,7 +80,10 @@ def get_wer(clip: ClipLoss, estimates: torch.Tensor, outputs: torch.Tensor, word
     when its word is among the ``topx`` most probable negatives (``wer``) / vocabulary words
     (``wer_vocab``).  The reference re-scans all N candidates once per test segment (a Python loop
     of GEMVs); here: ONE MFMA GEMM for all scores, a row-wise dot product for the own-target column,
-    a row softmax, a deterministic per-word segmented sum and two top-k passes."""
+    a row softmax, a deterministic per-word segmented sum and two top-k passes.
+
+    ``wer_random`` (`test.wer_random`, wer.py:95-96): every estimate is replaced by ``torch.randn_like`` of it, drawn on
+    the device per block of ``batch_size`` estimates (the reference draws per estimate); the chance level."""
     n = len(outputs)
     if n_negatives:
         perm = torch.randperm(n, generator=generator)
@@ -100,6 +110,8 @@ def get_wer(clip: ClipLoss, estimates: torch.Tensor, outputs: torch.Tensor, word
     correct = correct_vocab = 0.0
     for lo in range(0, len(estimates), batch_size):
         est = estimates[lo:lo + batch_size].cuda().contiguous()
+        if wer_random:
+            est = torch.randn_like(est)
         own = outputs[lo:lo + batch_size].cuda().contiguous()
         wh = word_hashes[lo:lo + batch_size].to(dev, torch.int64)
         m = est.shape[0]
@@ -124,3 +136,164 @@ def get_wer(clip: ClipLoss, estimates: torch.Tensor, outputs: torch.Tensor, word
         correct_vocab += float(hits_v.sum())
     total = len(estimates)
     return {"wer": 1 - correct / total, "wer_vocab": 1 - correct_vocab / total}
+
+
+# One flag word per device for the word labels (hip_ops.WORD_HASH_*_BIT), owned by this module like the dataset's
+# range flag -- NOT the Solver's flag word.  Read once per test epoch, after the last batch.
+_word_hash_flags: tp.Dict[torch.device, torch.Tensor] = {}
+
+
+def word_hash_flag(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    flag = _word_hash_flags.get(device)
+    if flag is None:
+        flag = _word_hash_flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
+    return flag
+
+
+def raise_if_word_hash_error(device) -> None:
+    """Synchronising check of the flag, which it clears."""
+    flag = word_hash_flag(device)
+    bits = int(flag.item())
+    if bits:
+        flag.zero_()
+    if bits & H.WORD_HASH_ALL_ZERO_BIT:
+        raise AssertionError("assert (wh != 0).all() (bm/wer.py:65): a kept segment has no word hash at check_at_time, "
+                             "one or two samples around it")
+    if bits & H.WORD_HASH_VALUE_BIT:
+        raise AssertionError("a word hash (bm/wer.py:58-65) is not finite, not an integer or not below 2^63 in magnitude")
+    if bits:
+        raise AssertionError("more kept segments than rows in the label array (bm/wer.py:66)")
+
+
+def check_at_time(tmin: float, sample_rate: float) -> int:
+    """bm/wer.py:46, the reference's expression: the sample of the window at which the word's hash is read."""
+    return int((-tmin) * sample_rate) + 2
+
+
+def wer_segments(segments, wer_recordings: tp.Optional[int] = None, wer_study: tp.Optional[str] = None):
+    """bm/wer.py:28-35 over a ``DeviceSegments``: the recordings that have segments (the reference's test datasets),
+    those of the study ``wer_study`` (``recording.study_name()``), the first ``wer_recordings`` of them."""
+    have = [i for i in range(len(segments.recordings)) if (segments.rec == i).any()]
+    picked = have
+    if wer_study is not None:
+        picked = [i for i in picked if segments.recordings[i].recording.study_name() == wer_study]
+    if wer_recordings is not None:
+        picked = picked[:wer_recordings]
+    return segments if picked == have else segments.subset(picked)
+
+
+def _free_bytes(device) -> int:
+    """What an allocation on ``device`` can still get: the driver's free memory plus what torch's allocator holds
+    unused."""
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(free) + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
+def collect_wer(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str],
+                check_at_time: int) -> tp.Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """bm/wer.py:24-25, 47-69, the collection loop: ``(estimates [n, ...], outputs [n, ...], word_hashes [n] int64)`` of
+    the kept segments of ``loader``'s device batches (at most ``total`` segments), all three views of resident device
+    arrays.  See ``wer_epoch``, which builds the loader."""
+    used_names = list(used_names)
+    channel = test_features.get_slice("WordHash").start
+    for model in solver._all_models():
+        model.train(False)
+    solver.loss.train(False)
+    estimates = outputs = hashes = flag = None
+    n = 0
+    with torch.no_grad():
+        for batch in loader:
+            features = test_features.extract_features(batch.features, used_names)
+            estimate, output, _, reject_mask = solver._process_batch(batch.replace(features=features))
+            if getattr(solver, "_gather", None) is not None and solver.feature_model is None:
+                solver._gather.wait()                       # whole-node negatives: nobody consumes the candidates here
+            if estimate is None:
+                continue
+            device = estimate.device
+            if estimates is None:
+                need = total * 4 * (estimate[0].numel() + output[0].numel()) + total * 8
+                free = _free_bytes(device)
+                if need > free:
+                    raise NotImplementedError(
+                        f"Not built: a host-memory spill for the test epoch -- the estimates and outputs of {total} "
+                        f"segments take {need} bytes on the device, {free} bytes are free")
+                estimates = torch.empty((total,) + tuple(estimate.shape[1:]), device=device, dtype=torch.float32)
+                outputs = torch.empty((total,) + tuple(output.shape[1:]), device=device, dtype=torch.float32)
+                hashes = torch.empty(total, device=device, dtype=torch.int64)
+                flag = word_hash_flag(device)
+                flag.zero_()                                # bits an epoch that ended in an exception left behind
+            m = estimate.shape[0]
+            if n + m > total:
+                raise ValueError(f"collect_wer: the loader delivers more than the announced {total} segments")
+            estimates[n:n + m].copy_(estimate)
+            outputs[n:n + m].copy_(output)
+            H.word_hash_pick(batch.features, channel, check_at_time, reject_mask.to(device), hashes, n, flag, count=m)
+            n += m
+    solver.check_pending_flags()
+    if n == 0:
+        raise RuntimeError("wer_epoch: every test segment was rejected (bm/wer.py:67 would concatenate an empty list)")
+    raise_if_word_hash_error(hashes.device)
+    return estimates[:n], outputs[:n], hashes[:n]
+
+
+def wer_from_loader(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str],
+                    check_at_time: int, *, wer_negatives: tp.Optional[int] = 10_000, wer_topx: int = 10,
+                    wer_random: bool = False, negatives_generator: tp.Optional[torch.Generator] = None):
+    """bm/wer.py:47-121 behind the loader: ``collect_wer``, then the ranking of ``get_wer``."""
+    estimates, outputs, hashes = collect_wer(solver, loader, total, test_features, used_names, check_at_time)
+    return get_wer(solver.loss, estimates, outputs, hashes, n_negatives=wer_negatives, topx=wer_topx,
+                   generator=negatives_generator, wer_random=wer_random)
+
+
+def wer_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, batch_size: int,
+              tmin: tp.Optional[float] = None, wer_negatives: tp.Optional[int] = 10_000, wer_topx: int = 10,
+              wer_random: bool = False, wer_recordings: tp.Optional[int] = None, wer_study: tp.Optional[str] = None,
+              generator: tp.Optional[torch.Generator] = None,
+              negatives_generator: tp.Optional[torch.Generator] = None) -> tp.Dict[str, float]:
+    """``get_wer(solver)`` of bm/wer.py:21-121 over a ``DeviceSegments`` test set: {"wer", "wer_vocab"}.
+
+    ``segments``: word-conditioned windows whose features builder ``test_features`` holds the used features plus
+    ``WordHash`` (`dset.features + extra_test_features`); ``used_names``: the features the model was trained on
+    (``solver.used_features.keys()``), cut out per batch by ``test_features.extract_features``.  ``wer_recordings`` /
+    ``wer_study`` / ``wer_negatives`` / ``wer_topx`` / ``wer_random``: `test.*` of the reference's configuration;
+    ``tmin``: `dset.test.tmin`, by default the segments' own.  ``generator`` shuffles the loader (bm/wer.py:36-37),
+    ``negatives_generator`` draws the ``randperm`` of the negatives (bm/wer.py:72).
+
+    Per batch, under ``no_grad`` and in eval mode: ``solver._process_batch`` on the batch with the extracted features;
+    a fully rejected batch is skipped; estimate and output are copied into two resident arrays (allocated for
+    ``len(segments)`` rows at the first batch's row shape) at the running row count, and ONE ``hip_ops.word_hash_pick``
+    launch writes the labels of the kept rows from the loader's own ``batch.features``.  Nothing is copied to the host:
+    the host waits only where ``_process_batch`` does (its asserts, a ``ScaleReject`` that counts its rejections) and
+    for the labels' flag word after the last batch -- ``AssertionError`` for the reference's ``assert (wh != 0).all()``.
+
+    Deviation: the label is the int64 of the fp32 hash, the reference's ``.int()`` wraps it to 32 bits; they agree for
+    hashes below 2^24 in magnitude (``WordHash(buckets=...)``).  Not built (``NotImplementedError``): more than one
+    rank (the reference shards the loader and averages the metrics), test sets whose two arrays do not fit on the
+    card (no host-memory spill); the soft WER is not computed."""
+    if distrib.world_size() > 1:
+        raise NotImplementedError("Not built: wer_epoch in a process group of more than one rank (the reference shards "
+                                  "the test loader over the ranks and averages the metrics, bm/wer.py:37, 121)")
+    if not isinstance(solver.loss, ClipLoss):
+        raise AssertionError(f"wer_epoch ranks with ClipLoss (bm/wer.py:87), the solver's loss is "
+                             f"{type(solver.loss).__name__}")
+    from .dataset import DeviceSegmentLoader
+    if segments.n_features != test_features.dimension:
+        raise ValueError(f"the segments carry {segments.n_features} feature channels, test_features describes "
+                         f"{test_features.dimension}")
+    used_names = list(used_names)
+    assert all([name in test_features for name in used_names])          # bm/features/base.py:152
+    channel = test_features.get_slice("WordHash").start
+    segments = wer_segments(segments, wer_recordings, wer_study)
+    total = len(segments)
+    if tmin is None:
+        tmin = segments.tmin
+    t0 = check_at_time(tmin, segments.sample_rate)
+    H.word_hash_pick_check((batch_size, test_features.dimension, segments.T), channel, t0, total, 0, 0)
+    if total == 0:
+        raise RuntimeError("wer_epoch: no test segment (bm/wer.py:67 would concatenate an empty list)")
+    loader = DeviceSegmentLoader(segments, batch_size, shuffle=True, generator=generator)
+    return wer_from_loader(solver, loader, total, test_features, used_names, t0, wer_negatives=wer_negatives,
+                           wer_topx=wer_topx, wer_random=wer_random, negatives_generator=negatives_generator)

@@ -599,3 +599,32 @@ class Solver:
             self._gather.wait()
         self.check_pending_flags()
         return estimate, output
+
+    def test_epoch(self, segments, **kw) -> tp.Dict[str, float]:
+        """bm/solver.py:435-448 (``_test_one_epoch``) over a ``dataset.DeviceSegments`` test set, pure dispatch.  With
+        ClipLoss: ``retrieval.wer_epoch(self, segments, **kw)`` (``test_features``, ``used_names``, ``batch_size`` and
+        the `test.wer_*` settings).  Otherwise ``metrics.regression_test_metrics`` over one loader per recording that has
+        segments: ``kw`` holds ``batch_size`` and, for the decode task, ``used_features`` (the features builder of the
+        model's output: ``metrics.metric_constructors``); the encode task takes ``metrics.encode_metric_constructors()``
+        and trims ``metrics.encode_trim_offset(sample_rate, segments.tmin, meg_init)`` samples."""
+        if isinstance(self.loss, ClipLoss):
+            from .retrieval import wer_epoch
+            return wer_epoch(self, segments, **kw)
+        from . import metrics as M
+        from .dataset import DeviceSegmentLoader
+        batch_size = kw.pop("batch_size")
+        used_features = kw.pop("used_features", None)
+        if kw:
+            raise TypeError(f"test_epoch: {sorted(kw)} belong to the ClipLoss test epoch (retrieval.wer_epoch)")
+        if self.task == "encode":
+            trim_offset = M.encode_trim_offset(self.sample_rate, segments.tmin, self.meg_init)
+            constructors = M.encode_metric_constructors()
+        else:
+            if used_features is None:
+                raise TypeError("test_epoch: the decode task's metrics need used_features, the features builder of the "
+                                "model's output (bm/solver.py:410-432)")
+            trim_offset = 0
+            constructors = M.metric_constructors(used_features)
+        loaders = [DeviceSegmentLoader(segments.only(i), batch_size) for i in range(len(segments.recordings))
+                   if (segments.rec == i).any()]
+        return M.regression_test_metrics(self, loaders, trim_offset, constructors)

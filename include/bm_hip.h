@@ -622,6 +622,18 @@ int bm_rowwise_dot(const float* a, const float* b, const float* scale, float* ou
 int bm_segment_sum_cols(const float* p, const int* order, const int* seg, float* pv, int rows, int cols,
                         int V, void* stream);
 
+/* ---- the word label of every kept test segment (wer.hip)  bm/wer.py:48, 58-66 ----
+ * x: the batch's full features fp32 [B][F][T], read in place; c: the channel of the WordHash feature; mask:
+ * reject_mask bytes [B] (non-zero = kept) or null (all kept).  For the kept rows in ascending order, rank r:
+ * dest[n0 + r] = (int64, the exact integer of the fp32 value) the first non-zero of x[t0], x[t0 - 1] (only if t0 > 0),
+ * x[t0 + 1], x[t0 - 2] (only if t0 > 1), x[t0 + 2]: the torch.where chain of bm/wer.py:58-64 over
+ * word_hash[reject_mask].  No other element of dest is written, nothing past dest_len.  *flag |= 1: every candidate of a
+ * kept row is zero (the assert of bm/wer.py:65; 0 is stored); 2: the value is not finite, not an integer or |v| >= 2^63;
+ * 4: n0 + r reached dest_len.  ONE launch of one workgroup, no atomics; the same bits on every run.
+ * t0 < 0, t0 + 2 >= T, c outside [0, F) and n0 outside [0, dest_len] are BM_ERR_ARG before any launch. */
+int bm_word_hash_pick(const float* x, int B, int F, int T, int c, int t0, const unsigned char* mask, long* dest,
+                      long dest_len, long n0, int* flag, void* stream);
+
 /* ---- fused Adam on the flat bucket (adam.hip)  torch.optim.Adam @ bm/train.py:118-119 ---- */
 int bm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, int step,
                  double lr, double beta1, double beta2, double eps, double grad_scale, void* stream);
