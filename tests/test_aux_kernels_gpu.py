@@ -8,9 +8,10 @@ Style and tolerances are tests/test_row_kernels_gpu.py's: floating-point results
 same expression in fp32 on the CPU, both against fp64, both printed; an input on which plain fp32 is marginal is
 replaced, not tolerated); integer results and fixed-order sums are compared exactly.
 
-NOT covered here: BatchNorm statistics of a channel whose mean dwarfs its spread.  The finalize kernels form the
-variance as E[x^2] - E[x]^2 from fp32 partial sums, which cancels when |mean| >> std; the data below keeps every
-channel's |mean| within a few standard deviations, so nothing in this file says how the kernels behave beyond that."""
+BatchNorm statistics of a channel whose mean dwarfs its spread -- the finalize kernels form the variance as
+E[x^2] - E[x]^2 from fp32 partial sums, which cancels when |mean| >> std, and the data below keeps every channel's |mean|
+within a few standard deviations -- are held in tests/test_bn_conditioning_gpu.py (every producer of partials on a ladder
+of |mean| / std up to 1000, the law the variance error obeys, the envelope R_SAFE of the whole chain)."""
 import math
 
 import pytest
