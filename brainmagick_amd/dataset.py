@@ -19,7 +19,7 @@ The features of a batch come either from full-length arrays (two more gathers) o
 (``DeviceRecording(meg, events=features.DeviceEvents(...))``): then ONE ``hip_ops.segment_features`` launch builds the
 features and the mask of the batch by the reference's per-window rules (features.py, csrc/features.hip).
 
-Not built: WordPulse / PhonemePulse (``post_process``), Wav2VecChunk, the batch's ``_event_lists``, computing the
+Not built: WordPulse / PhonemePulse (``post_process``), Wav2VecChunk, computing the
 wav2vec2 states / embeddings themselves (the mel spectrogram and the pitch: ``audio.py``), ``autoreject``,
 ``split_wav_as_block``, ``decim != 1``, channel picking, reading ``.fif`` files, ``mne.Info`` and layouts.  There is no CPU
 fallback.

@@ -19,7 +19,12 @@ Three rules, named for what they do, cover the reference's features:
 - ``chunk``: one array ``[D, L]`` per event; ``_get_cached_tensor`` + ``get_on_overlap`` of bm/features/audio.py:211-274
   (Wav2VecTransformer, Wav2VecConvolution).
 
-Not built: WordPulse and PhonemePulse (``post_process``), Wav2VecChunk, the batch's ``_event_lists``, and computing the
+The batch's ``_event_lists`` have one reader in the reference, ``_get_extra_info`` of scripts/run_eval_probs.py:27-57 (the
+word index and the sentence of the word at ``check_at_time``).  What it reads travels with the word events as two
+optional integer columns, ``word_index`` and ``sequence_id`` (``DeviceEvents``), and ``hip_ops.segment_eval_labels`` looks
+the word up in the resident tables (``retrieval.segment_eval_epoch``); no list of events is built per batch.
+
+Not built: WordPulse and PhonemePulse (``post_process``), Wav2VecChunk, and computing the
 wav2vec2 hidden states / the word embeddings themselves (the mel spectrogram's and the pitch's arrays come from
 ``audio.DeviceMelSpectrum.compute`` and ``audio.DevicePitch.compute``, resampled to 16 kHz on the device when asked).
 There is no CPU fallback.
@@ -31,6 +36,8 @@ import numpy as np
 import torch
 
 RULES = ("constant", "resampled", "chunk")
+WORD_KIND = "word"
+WORD_INFO_COLUMNS = ("word_index", "sequence_id")              # optional integer columns of the word events
 
 
 class EventFeature:
@@ -158,6 +165,12 @@ class DeviceEvents:
     travels with the events: with it two wavefront-wide searches bound a window's candidates, and the kernel tests
     every event between the bounds.
 
+    The ``word`` kind takes two optional integer columns, ``"word_index"`` and ``"sequence_id"`` (each ``[n]``, both or
+    none, non-negative): ``event.word_index`` and an integer the caller maps ``event.word_sequence`` to (Python's salted
+    ``hash`` stays with the caller, as for ``WordHash``).  They stay resident as int64 (``word_info`` ``[n, 2]``) for the
+    segment-level evaluation; without them nothing changes.  ``ValueError`` when one is missing, a length differs from
+    ``n`` or a value is negative.
+
     ``ValueError`` names the first event whose ``start`` is below its predecessor's (or not finite), whose duration is
     negative, whose resampled length ``round(((start + duration) - start) * sample_rate)`` is below 1, or -- for a chunk
     feature with ``duration >= 0.5`` -- whose ``L / duration`` is outside (42, 52), the reference's assert
@@ -172,10 +185,14 @@ class DeviceEvents:
         self.n_events: tp.Dict[str, int] = {}
         self.kind_tables: tp.List[tp.Optional[tp.Tuple[torch.Tensor, ...]]] = []
         self.sources: tp.List[tp.Any] = [None] * len(builder)
+        self.word_info: tp.Optional[torch.Tensor] = None       # [n, 2] int64 on the device: word_index, sequence_id
+        self.word_info_host: tp.Optional[np.ndarray] = None    # the same on the host, for the dense segment ids
         for kind in builder.kinds:
             table = events.get(kind)
             n = 0 if table is None else len(table["start"])
             self.n_events[kind] = n
+            if kind == WORD_KIND and table is not None:
+                self._adopt_word_info(table, n)
             if n == 0:
                 self.kind_tables.append(None)
                 continue
@@ -231,8 +248,31 @@ class DeviceEvents:
                     arrays.append(a.to(device=self.device, dtype=torch.float32).contiguous())
                 self.sources[f] = (arrays, ers)
 
+    def _adopt_word_info(self, table: tp.Mapping[str, tp.Any], n: int) -> None:
+        given = [c for c in WORD_INFO_COLUMNS if c in table]
+        if not given:
+            return
+        if len(given) != len(WORD_INFO_COLUMNS):
+            raise ValueError(f"{WORD_KIND} events carry {given[0]!r} without "
+                             f"{[c for c in WORD_INFO_COLUMNS if c not in table][0]!r}: the word information is both or none")
+        columns = []
+        for c in WORD_INFO_COLUMNS:
+            raw = np.asarray(table[c])
+            if raw.ndim != 1 or len(raw) != n:
+                raise ValueError(f"{c}: shape {raw.shape} for {n} {WORD_KIND} events")
+            if raw.dtype.kind not in "iu" and not (raw.dtype.kind == "f" and np.array_equal(raw, np.trunc(raw))):
+                raise ValueError(f"{c}: {raw.dtype} values that are not integers")
+            if n and raw.min() < 0:
+                raise ValueError(f"{c}: event {int(np.argmax(raw < 0))} is {raw[np.argmax(raw < 0)]}; the values are "
+                                 "non-negative integers (-1 stands for \"no word\" in the evaluation's labels)")
+            columns.append(raw.astype(np.int64))
+        self.word_info_host = np.ascontiguousarray(np.stack(columns, axis=1)).reshape(n, 2)
+        self.word_info = torch.from_numpy(self.word_info_host).to(self.device)
+
     def resident_bytes(self) -> int:
         total = sum(t.numel() * t.element_size() for k in self.kind_tables if k is not None for t in k)
+        if self.word_info is not None:
+            total += self.word_info.numel() * self.word_info.element_size()
         for s in self.sources:
             if isinstance(s, torch.Tensor):
                 total += s.numel() * s.element_size()

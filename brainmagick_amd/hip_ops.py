@@ -2288,3 +2288,158 @@ def word_hash_pick(features: torch.Tensor, c: int, check_at_time: int, reject_ma
         check(lib().bm_word_hash_pick(_p(features), B, F, T, int(c), int(check_at_time), _p(reject_mask), _p(dest),
                                       dest.numel(), int(n0), _p(flag), _stream()), "bm_word_hash_pick")
     _timed("word_hash_pick", 0., launch)
+
+
+# The labels of the segment-level evaluation (csrc/segment_eval.hip, scripts/run_eval_probs.py:27-57, 105-158).
+SEGMENT_EVAL_COLUMNS = ("word_hash", "word_index", "sequence_id", "segment_id", "subject_index", "recording_index",
+                        "word_event")
+SEGMENT_EVAL_VALUE_BIT = 1      # the word hash is not finite, not an integer, or |v| >= 2^63
+SEGMENT_EVAL_DEST_BIT = 2       # a kept row had no row of dest left
+SEGMENT_EVAL_RANGE_BIT = 4      # a recording index outside the tables (the row gets the no-word values)
+FIRST_OCCURRENCE_RANGE_BIT = 8  # an id outside [0, n_ids) (the row is masked out)
+
+
+class WordInfoTable:
+    """The device table of ``bm_segment_eval_labels`` for the word information: per recording None (it is not part of
+    the evaluated set) or an int64 array ``[n_words, 3]`` = ``(word_index, sequence_id, segment_id)`` in the order of the
+    recording's word events (a numpy array or a tensor; uploaded once, the table keeps it alive).  ``n_ids``: segment ids
+    are in ``[0, n_ids)``, 0 = no word."""
+
+    def __init__(self, rows: tp.Sequence[tp.Any], n_ids: int, device):
+        L = lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise BmHipError("word-info table: not on a GPU; the evaluation's labels are a HIP kernel and have no CPU "
+                             "fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        entry = L.bm_segment_eval_info_entry_bytes()
+        host = torch.zeros(max(len(rows), 1), entry, dtype=torch.uint8)
+        self.arrays: tp.List[tp.Optional[torch.Tensor]] = []
+        for r, a in enumerate(rows):
+            if a is None:
+                self.arrays.append(None)
+                continue
+            a = torch.as_tensor(a)
+            if a.dim() != 2 or a.shape[1] != 3 or a.dtype != torch.int64:
+                raise BmHipError(f"word-info table: recording {r}: {a.dtype} of shape {tuple(a.shape)}, expected int64 "
+                                 "[n_words, 3]")
+            a = a.to(self.device).contiguous()
+            check(L.bm_segment_eval_info_fill(ctypes.c_void_p(host[r].data_ptr()), _p(a) if a.numel() else None,
+                                              a.shape[0]), "bm_segment_eval_info_fill")
+            self.arrays.append(a)
+        self.n_recordings, self.n_ids = len(rows), int(n_ids)
+        self.table = host.to(self.device)
+
+    def __len__(self) -> int:
+        return self.n_recordings
+
+
+def segment_eval_labels_check(shape: tp.Sequence[int], c: int, check_at_time: int, dest_shape: tp.Sequence[int],
+                              n0: int = 0, count: tp.Optional[int] = None) -> None:
+    """The ``ValueError``s of ``segment_eval_labels`` that come from the shapes alone (nothing is launched, no tensor is
+    touched): features that are not ``[B, F_all, T]``; ``check_at_time < 0`` or ``check_at_time + 1 >= T`` (the
+    reference's ``word_hash[:, check_at_time + 1]`` would wrap around or raise ``IndexError``); ``c`` outside
+    ``[0, F_all)``; a ``dest`` that is not ``[rows, 7]``; a negative ``n0``; fewer than ``n0 + count`` rows (``count``:
+    the kept rows when the caller knows them, else all ``B``)."""
+    if len(shape) != 3:
+        raise ValueError(f"segment_eval_labels: the features are {tuple(shape)}, expected [B, F_all, T]")
+    B, F, T = (int(s) for s in shape)
+    if check_at_time < 0 or check_at_time + 1 >= T:
+        raise ValueError(f"segment_eval_labels: check_at_time = {check_at_time} reads the samples {check_at_time - 1} .. "
+                         f"{check_at_time + 1} of a window of {T} (scripts/run_eval_probs.py:116-130 would wrap around "
+                         "or raise IndexError)")
+    if not 0 <= c < F:
+        raise ValueError(f"segment_eval_labels: channel {c} of {F}")
+    if len(dest_shape) != 2 or int(dest_shape[1]) != len(SEGMENT_EVAL_COLUMNS):
+        raise ValueError(f"segment_eval_labels: dest is {tuple(dest_shape)}, expected [rows, {len(SEGMENT_EVAL_COLUMNS)}]")
+    count = B if count is None else int(count)
+    if not 0 <= count <= B:
+        raise ValueError(f"segment_eval_labels: {count} kept rows of a batch of {B}")
+    if n0 < 0 or n0 + count > int(dest_shape[0]):
+        raise ValueError(f"segment_eval_labels: dest holds {int(dest_shape[0])} rows, the batch writes {n0} .. "
+                         f"{n0 + count - 1}")
+
+
+def segment_eval_labels(features: torch.Tensor, c: int, check_at_time: int, reject_mask: tp.Optional[torch.Tensor],
+                        arrays: tp.Mapping[str, torch.Tensor], first: int, events: "EventTable", word_kind: int,
+                        infos: WordInfoTable, sample_rate: float, dest: torch.Tensor, n0: int, flag: torch.Tensor,
+                        count: tp.Optional[int] = None) -> None:
+    """``dest[n0 + r]`` = the seven labels (``SEGMENT_EVAL_COLUMNS``) of the kept row of rank ``r`` of the batch whose
+    full ``features`` ``[B, F_all, T]`` (fp32, contiguous, read in place) were built for the segments ``first ... first +
+    B - 1`` of the epoch's ``arrays`` (``DeviceSegmentLoader.epoch_arrays``: ``rec``, ``wstart``, ``subject_index``,
+    ``recording_index``): ``_get_extra_info`` and scripts/run_eval_probs.py:105-130, 155-158 as ONE launch
+    (``bm_segment_eval_labels``).  ``events``: the segments' ``EventTable``, ``word_kind`` the slot of its word events;
+    ``infos``: the ``WordInfoTable`` of the evaluated set; ``dest``: int64 ``[rows, 7]``, contiguous; ``flag``: one int32
+    on the device, see the ``SEGMENT_EVAL_*_BIT``s.  ``ValueError``s (``segment_eval_labels_check``, and events without
+    words or word information) before any launch."""
+    if not isinstance(features, torch.Tensor) or not isinstance(dest, torch.Tensor):
+        raise BmHipError("segment_eval_labels: features and dest are tensors")
+    segment_eval_labels_check(features.shape, c, check_at_time, dest.shape, n0, count)
+    if events is None or infos is None:
+        raise ValueError("segment_eval_labels: the segments carry no events or no word information (word_index / "
+                         "sequence_id columns of the word events)")
+    if not 0 <= word_kind < events.n_kinds:
+        raise ValueError(f"segment_eval_labels: the word kind {word_kind} of {events.n_kinds} event kinds")
+    if len(infos) != len(events):
+        raise ValueError(f"segment_eval_labels: word information for {len(infos)} recordings, events for {len(events)}")
+    _req(features, "segment_eval_labels.features")
+    _req(dest, "segment_eval_labels.dest", torch.int64)
+    _req(flag, "segment_eval_labels.flag", torch.int32)
+    B, F, T = features.shape
+    if reject_mask is not None:
+        _req(reject_mask, "segment_eval_labels.reject_mask", torch.bool)
+        if reject_mask.shape != (B,):
+            raise ValueError(f"segment_eval_labels: reject_mask is {tuple(reject_mask.shape)} for a batch of {B}")
+    rec, wstart = arrays["rec"], arrays["wstart"]
+    subject, recording = arrays["subject_index"], arrays["recording_index"]
+    _req(rec, "segment_eval_labels.rec", torch.int32)
+    _req(wstart, "segment_eval_labels.wstart", torch.float64)
+    _req(subject, "segment_eval_labels.subject_index", torch.int64)
+    _req(recording, "segment_eval_labels.recording_index", torch.int64)
+    n_index = rec.numel()
+    if wstart.numel() != n_index or subject.numel() != n_index or recording.numel() != n_index or flag.numel() < 1:
+        raise BmHipError("segment_eval_labels: the epoch's arrays differ in length, or the flag is empty")
+    if first < 0 or first + B > n_index:
+        raise ValueError(f"segment_eval_labels: segments {first} .. {first + B - 1} of an epoch of {n_index}")
+    for name, t in (("rec", rec), ("wstart", wstart), ("subject_index", subject), ("recording_index", recording),
+                    ("flag", flag), ("dest", dest), ("features", features), ("reject_mask", reject_mask)):
+        if t is not None and t.device != events.device:
+            raise BmHipError(f"segment_eval_labels: {name} is on {t.device}, the event table on {events.device}")
+
+    def launch():
+        check(lib().bm_segment_eval_labels(_p(features), B, F, T, int(c), int(check_at_time), _p(reject_mask), _p(rec),
+                                           _p(wstart), _p(subject), _p(recording), n_index, int(first), _p(events.kinds),
+                                           events.n_kinds, int(word_kind), _p(infos.table), len(infos),
+                                           float(sample_rate), _p(dest), dest.shape[0], int(n0), _p(flag), _stream()),
+              "bm_segment_eval_labels")
+    _timed("segment_eval_labels", 0., launch)
+
+
+def first_occurrence(ids: torch.Tensor, n_ids: int, flag: tp.Optional[torch.Tensor] = None):
+    """``(mask [N] bool, first_row [N] int32)`` of ``ids`` (int64 ``[N]``, values in ``[0, n_ids)``): ``mask[i]`` is true
+    when row ``i`` is the first that carries its id, ``first_row[i]`` is that first row -- the ``seen_segment_hashes``
+    loop of scripts/run_eval_probs.py:141-149 over a whole epoch, two launches (``bm_first_occurrence``: an integer
+    ``atomicMin`` per row into a table of ``n_ids`` entries, then one compare per row; the same result on every run).
+    An id out of range raises ``FIRST_OCCURRENCE_RANGE_BIT`` in ``flag`` (one int32 on the device), its row is masked
+    out and its ``first_row`` is -1.  ``N < 2^31``."""
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+        raise ValueError("first_occurrence: ids is a one-dimensional tensor")
+    N = ids.numel()
+    if N >= 2 ** 31:
+        raise ValueError(f"first_occurrence: {N} rows; N < 2^31")
+    if n_ids < 0:
+        raise ValueError(f"first_occurrence: n_ids = {n_ids}")
+    _req(ids, "first_occurrence.ids", torch.int64)
+    if flag is None:
+        flag = torch.zeros(1, device=ids.device, dtype=torch.int32)
+    _req(flag, "first_occurrence.flag", torch.int32)
+    first = torch.full((max(int(n_ids), 1),), 2 ** 31 - 1, device=ids.device, dtype=torch.int32)
+    mask = torch.empty(N, device=ids.device, dtype=torch.bool)
+    first_row = torch.empty(N, device=ids.device, dtype=torch.int32)
+
+    def launch():
+        check(lib().bm_first_occurrence(_p(ids), N, int(n_ids), _p(first), _p(mask), _p(first_row), _p(flag), _stream()),
+              "bm_first_occurrence")
+    _timed("first_occurrence", 0., launch)
+    return mask, first_row

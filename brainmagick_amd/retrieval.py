@@ -13,13 +13,21 @@ the outputs and the word label of every kept segment of a ``dataset.DeviceSegmen
 (bm/wer.py:24-69; the labels by ONE ``hip_ops.word_hash_pick`` launch per batch) and hands them to ``get_wer``
 (bm/wer.py:71-121).  Not built: a process group of more than one rank, a host-memory spill of the two arrays, and the
 soft WER, which the reference computes and never returns.
+
+``segment_eval_epoch`` is the first half of the headline metric, ``_load_test_data`` + ``run_eval``
+(scripts/run_eval_probs.py:60-180, 310-382): it collects predictions, outputs and seven labels per kept test segment in
+resident arrays (ONE ``hip_ops.segment_eval_labels`` launch per batch: the word hash at ``check_at_time``, and the word
+index, sentence and segment of the word event that covers it, read from the resident event tables), de-duplicates the
+candidates with ``hip_ops.first_occurrence`` and ranks with ``builds_probs`` + ``get_accuracy_from_probs``.
 """
 import typing as tp
 
+import numpy as np
 import torch
 
 from . import distrib
 from . import hip_ops as H
+from .features import WORD_KIND
 from .losses import ClipLoss
 
 
@@ -51,10 +59,15 @@ def get_accuracy_from_probs(probs: torch.Tensor, target_labels: torch.Tensor,
     """scripts/run_eval_probs.py:237-264.  probs [B, V]; target_labels [B]; vocab_labels [V]."""
     assert len(target_labels) == len(probs)
     assert len(vocab_labels) == probs.shape[1]
+    return _topk_hits(probs, target_labels, vocab_labels, topk).float().mean().item()
+
+
+def _topk_hits(probs: torch.Tensor, target_labels: torch.Tensor, vocab_labels: torch.Tensor, topk: int) -> torch.Tensor:
+    """[B] int32: 1 where the row's own label is among the labels of its ``topk`` most probable columns."""
     _, _, hits = H.topk_rows(probs.contiguous(), topk,
                              vocab_labels.to(probs.device, torch.int64).contiguous(),
                              target_labels.to(probs.device, torch.int64).contiguous())
-    return hits.float().mean().item()
+    return hits
 
 
 def segment_topk_accuracy(clip: ClipLoss, preds: torch.Tensor, trues: torch.Tensor,
@@ -297,3 +310,223 @@ def wer_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, 
     loader = DeviceSegmentLoader(segments, batch_size, shuffle=True, generator=generator)
     return wer_from_loader(solver, loader, total, test_features, used_names, t0, wer_negatives=wer_negatives,
                            wer_topx=wer_topx, wer_random=wer_random, negatives_generator=negatives_generator)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The segment-level evaluation, scripts/run_eval_probs.py: _load_test_data (:60-180) + run_eval (:310-382)
+# ---------------------------------------------------------------------------------------------------------------------
+METADATA_KEYS = ("word_hashes", "word_indices", "seq_indices", "segment_hashes", "subject_id", "recording_id",
+                 "word_event")                          # the columns of hip_ops.SEGMENT_EVAL_COLUMNS, in that order
+
+# One flag word per device for the evaluation's labels and the first occurrences (hip_ops.SEGMENT_EVAL_*_BIT,
+# FIRST_OCCURRENCE_RANGE_BIT), owned by this module.  Read once per evaluation, after the first-occurrence launches.
+_segment_eval_flags: tp.Dict[torch.device, torch.Tensor] = {}
+
+
+def segment_eval_flag(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    flag = _segment_eval_flags.get(device)
+    if flag is None:
+        flag = _segment_eval_flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
+    return flag
+
+
+def raise_if_segment_eval_error(device) -> None:
+    """Synchronising check of the flag, which it clears."""
+    flag = segment_eval_flag(device)
+    bits = int(flag.item())
+    if bits:
+        flag.zero_()
+    if bits & H.SEGMENT_EVAL_VALUE_BIT:
+        raise AssertionError("a word hash (scripts/run_eval_probs.py:116-130) is not finite, not an integer or not below "
+                             "2^63 in magnitude")
+    if bits & H.SEGMENT_EVAL_RANGE_BIT:
+        raise IndexError("a test segment's recording index is outside the word tables")
+    if bits & H.FIRST_OCCURRENCE_RANGE_BIT:
+        raise IndexError("a segment id is outside the dense ids of the evaluated set")
+    if bits:
+        raise AssertionError("more kept segments than rows in the label array (scripts/run_eval_probs.py:132)")
+
+
+def dense_segment_ids(word_info: tp.Sequence[tp.Optional[np.ndarray]]):
+    """``(rows, n_ids)``: per recording None or int64 ``[n_words, 3]`` = ``(word_index, sequence_id, segment_id)``, the
+    segment id dense over the distinct ``(sequence_id, word_index)`` pairs of all the recordings given (``word_info``:
+    their ``DeviceEvents.word_info_host`` ``[n_words, 2]``, None for a recording outside the evaluated set), in the
+    pairs' sorted order and starting at 1 -- the equality structure of ``hash(f"{sid}_{wid}")``
+    (scripts/run_eval_probs.py:137-139).  Id 0 is kept for "no word", the reference's ``hash("-1_-1")``; ``n_ids``
+    counts it.  Pure numpy, once per evaluated set."""
+    given = [w for w in word_info if w is not None]
+    if not given:
+        return [None] * len(word_info), 1
+    pairs = np.concatenate([np.asarray(w, dtype=np.int64).reshape(-1, 2)[:, ::-1] for w in given])     # (sequence, word)
+    distinct, inverse = np.unique(pairs, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    rows, at = [], 0
+    for w in word_info:
+        if w is None:
+            rows.append(None)
+            continue
+        w = np.asarray(w, dtype=np.int64).reshape(-1, 2)
+        rows.append(np.ascontiguousarray(np.concatenate([w, inverse[at:at + len(w), None] + 1], axis=1)))
+        at += len(w)
+    return rows, len(distinct) + 1
+
+
+def collect_segment_eval(solver, loader, total: int, test_features, used_names: tp.Sequence[str], check_at_time: int,
+                         infos: "H.WordInfoTable") -> tp.Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The loop of ``_load_test_data`` (scripts/run_eval_probs.py:95-158) over a ``DeviceSegmentLoader``: ``(preds [n,
+    ...], trues [n, ...], labels [n, 7] int64)`` of the kept segments, views of resident device arrays; the structure of
+    ``collect_wer``.  ``trues`` is every kept row's output: the de-duplication happens once, over the epoch."""
+    used_names = list(used_names)
+    segments = loader.segments
+    channel = test_features.get_slice("WordHash").start
+    word_kind = segments.builder.kinds.index(WORD_KIND)
+    events = segments.tables()[1]
+    for model in solver._all_models():
+        model.train(False)
+    solver.loss.train(False)
+    preds = trues = labels = None
+    flag = segment_eval_flag(segments.device)
+    flag.zero_()                                            # bits an evaluation that ended in an exception left behind
+    n = 0
+    with torch.no_grad():
+        for k, batch in enumerate(loader):
+            features = test_features.extract_features(batch.features, used_names)
+            estimate, output, _, reject_mask = solver._process_batch(batch.replace(features=features))
+            if getattr(solver, "_gather", None) is not None and solver.feature_model is None:
+                solver._gather.wait()
+            if estimate is None:
+                continue
+            device = estimate.device
+            if preds is None:
+                need = total * 4 * (estimate[0].numel() + output[0].numel()) + total * 8 * len(METADATA_KEYS)
+                free = _free_bytes(device)
+                if need > free:
+                    raise NotImplementedError(
+                        f"Not built: a host-memory spill for the segment-level evaluation -- the predictions, outputs "
+                        f"and labels of {total} segments take {need} bytes on the device, {free} bytes are free")
+                preds = torch.empty((total,) + tuple(estimate.shape[1:]), device=device, dtype=torch.float32)
+                trues = torch.empty((total,) + tuple(output.shape[1:]), device=device, dtype=torch.float32)
+                labels = torch.empty(total, len(METADATA_KEYS), device=device, dtype=torch.int64)
+            m = estimate.shape[0]
+            if n + m > total:
+                raise ValueError(f"collect_segment_eval: the loader delivers more than the announced {total} segments")
+            preds[n:n + m].copy_(estimate)
+            trues[n:n + m].copy_(output)
+            H.segment_eval_labels(batch.features, channel, check_at_time, reject_mask.to(device), loader.epoch_arrays,
+                                  k * loader.batch_size, events, word_kind, infos, segments.sample_rate, labels, n, flag,
+                                  count=m)
+            n += m
+    solver.check_pending_flags()
+    if n == 0:
+        raise RuntimeError("segment_eval_epoch: every test segment was rejected (scripts/run_eval_probs.py:179 would "
+                           "concatenate an empty list)")
+    return preds[:n], trues[:n], labels[:n]
+
+
+def segment_eval_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, batch_size: int,
+                       tmin: tp.Optional[float] = None, n_recordings: tp.Optional[int] = None,
+                       test_study: tp.Optional[str] = None, topks: tp.Sequence[int] = (1, 5, 10),
+                       probs_batch_size: int = 1000, n_negatives: int = 20_000, shuffle: bool = False,
+                       generator: tp.Optional[torch.Generator] = None, return_probs: bool = False,
+                       clip: tp.Optional[tp.Mapping[str, tp.Any]] = None) -> tp.Dict[str, tp.Any]:
+    """The segment-level evaluation of scripts/run_eval_probs.py over a ``DeviceSegments`` test set: the collection of
+    ``_load_test_data`` (:60-180), then ``run_eval`` (:310-382) -- the paper's top-k accuracy over unique audio
+    segments.
+
+    ``segments``: word-conditioned windows over recordings with events whose word events carry ``word_index`` and
+    ``sequence_id`` (``features.DeviceEvents``) and whose builder ``test_features`` holds the used features plus
+    ``WordHash``; ``used_names``: the features the model was trained on.  ``n_recordings`` / ``test_study``: as
+    ``wer_segments`` picks recordings; ``tmin``: `dset.test.tmin`, by default the segments' own; ``shuffle`` /
+    ``generator``: the loader's order (``Evaluator.shuffle_test_data``); ``topks``, ``probs_batch_size``,
+    ``n_negatives``: `run_eval`'s.  A solver whose loss is not a ClipLoss ranks with ``ClipLoss(**clip)`` (:318-322).
+
+    Once per evaluated set the host numbers the distinct ``(sequence_id, word_index)`` pairs (``dense_segment_ids``:
+    numpy; 0 = no word) and uploads one ``[n_words, 3]`` array per recording.  Per batch, under ``no_grad`` and in eval
+    mode: ``solver._process_batch`` on the batch with the extracted features; a fully rejected batch is skipped;
+    prediction and output are copied into two resident arrays at the running row count and ONE
+    ``hip_ops.segment_eval_labels`` launch writes the seven labels of the kept rows.  Nothing is copied to the host: the
+    host waits only where ``_process_batch`` does, and once for the flag word.  Then ``hip_ops.first_occurrence`` over the
+    segment ids gives ``trues = outputs[mask]`` and ``vocab_segment = segment_id[mask]`` (first occurrences in row order
+    do not depend on the batching), and per ``k`` the accuracy is ``builds_probs`` + ``get_accuracy_from_probs`` with the
+    segment ids as labels -- block by block over ``probs_batch_size`` predictions, so that the ``[N, V]`` matrix is
+    never resident, unless ``return_probs`` asks for it.
+
+    Returns ``{"acc": {k: accuracy}, "metadata": {key: int64 device tensor [N]} for METADATA_KEYS (the reference's
+    names, plus "word_event": the index of the word in its recording's word table, -1 without one), "vocab_segment",
+    "negative_stats": the five counts of :371-377, "probs_segment" (with return_probs)}``.
+
+    Deviation: the reference squeezes ``hash(word_sequence)`` through an fp32 tensor before ``.long()``; the ids here
+    are exact int64.  The two agree wherever the caller's ids are below 2^24.  Segment "hashes" are the dense ids, not
+    Python hashes: only their equality structure is the reference's.
+
+    Not built: the string columns (``word_strings``, ``word_segment_strings``, ``study``, ``*_uid``; ``word_event`` and
+    ``recording_id`` let a caller look them up), the reference's fallback that hashes the word strings when the
+    builder has no ``WordHash`` (``ValueError``), the files on disk, ``Evaluator`` / ``EvalJob`` / submitit, more than
+    one rank and a host-memory spill (``NotImplementedError``)."""
+    if distrib.world_size() > 1:
+        raise NotImplementedError("Not built: segment_eval_epoch in a process group of more than one rank")
+    if "WordHash" not in test_features:
+        raise ValueError("segment_eval_epoch: the features builder has no WordHash; the reference's fallback that hashes "
+                         "the word strings (scripts/run_eval_probs.py:110-113) is not built")
+    if getattr(segments, "builder", None) is None:
+        raise ValueError("segment_eval_epoch: the segments carry no events (full-length feature arrays hold no words)")
+    if segments.n_features != test_features.dimension:
+        raise ValueError(f"the segments carry {segments.n_features} feature channels, test_features describes "
+                         f"{test_features.dimension}")
+    used_names = list(used_names)
+    assert all([name in test_features for name in used_names])          # bm/features/base.py:152
+    channel = test_features.get_slice("WordHash").start
+    segments = wer_segments(segments, n_recordings, test_study)
+    total = len(segments)
+    evaluated = sorted(set(int(r) for r in segments.rec))
+    for r in evaluated:
+        if segments.recordings[r].events.word_info_host is None:
+            raise ValueError(f"segment_eval_epoch: the word events of recording {r} carry no word_index / sequence_id "
+                             "columns (features.DeviceEvents)")
+    if tmin is None:
+        tmin = segments.tmin
+    t0 = check_at_time(tmin, segments.sample_rate)
+    H.segment_eval_labels_check((batch_size, test_features.dimension, segments.T), channel, t0,
+                                (total, len(METADATA_KEYS)), 0, 0)
+    if total == 0:
+        raise RuntimeError("segment_eval_epoch: no test segment")
+    clip_loss = solver.loss if isinstance(solver.loss, ClipLoss) else ClipLoss(**dict(clip or {})).to(segments.device)
+    from .dataset import DeviceSegmentLoader
+    rows, n_ids = dense_segment_ids([segments.recordings[r].events.word_info_host if r in evaluated else None
+                                     for r in range(len(segments.recordings))])
+    infos = H.WordInfoTable(rows, n_ids, segments.device)
+    loader = DeviceSegmentLoader(segments, batch_size, shuffle=shuffle, generator=generator)
+    preds, outputs, labels = collect_segment_eval(solver, loader, total, test_features, used_names, t0, infos)
+    device = labels.device
+    columns = labels.t().contiguous()
+    metadata = dict(zip(METADATA_KEYS, columns))
+    segment_id = metadata["segment_hashes"]
+    mask, _ = H.first_occurrence(segment_id, n_ids, segment_eval_flag(device))
+    raise_if_segment_eval_error(device)
+    trues = outputs[mask]
+    vocab_segment = segment_id[mask]
+    n = len(preds)
+    result: tp.Dict[str, tp.Any] = {}
+    if return_probs:
+        probs = builds_probs(clip_loss, preds, trues, batch_size=probs_batch_size)
+        acc = {k: get_accuracy_from_probs(probs, segment_id, vocab_segment, topk=k) for k in topks}
+        result["probs_segment"] = probs
+    else:
+        hits = {k: torch.zeros((), device=device, dtype=torch.int64) for k in topks}
+        for lo in range(0, n, probs_batch_size):
+            block = builds_probs(clip_loss, preds[lo:lo + probs_batch_size], trues, batch_size=probs_batch_size)
+            for k in topks:
+                hits[k] += _topk_hits(block, segment_id[lo:lo + probs_batch_size], vocab_segment, k).sum()
+        acc = {k: int(hits[k]) / n for k in topks}
+    word_hashes = metadata["word_hashes"]
+    result.update(acc=acc, metadata=metadata, vocab_segment=vocab_segment, negative_stats={
+        "n_test_samples": n,
+        "n_test_vocab": len(torch.unique(word_hashes)),
+        "n_test_segments": len(torch.unique(segment_id)),
+        "n_neg_samples": len(word_hashes[:n_negatives]),
+        "n_neg_segments": len(torch.unique(segment_id[:n_negatives])),
+    })
+    return result

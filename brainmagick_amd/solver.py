@@ -628,3 +628,10 @@ class Solver:
         loaders = [DeviceSegmentLoader(segments.only(i), batch_size) for i in range(len(segments.recordings))
                    if (segments.rec == i).any()]
         return M.regression_test_metrics(self, loaders, trim_offset, constructors)
+
+    def segment_eval(self, segments, **kw) -> tp.Dict[str, tp.Any]:
+        """The segment-level evaluation of scripts/run_eval_probs.py (the paper's top-k accuracy over unique audio
+        segments) over a ``dataset.DeviceSegments`` test set, pure dispatch: ``retrieval.segment_eval_epoch(self,
+        segments, **kw)`` (``test_features``, ``used_names``, ``batch_size`` and `run_eval`'s settings)."""
+        from . import retrieval
+        return retrieval.segment_eval_epoch(self, segments, **kw)

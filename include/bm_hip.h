@@ -634,6 +634,36 @@ int bm_segment_sum_cols(const float* p, const int* order, const int* seg, float*
 int bm_word_hash_pick(const float* x, int B, int F, int T, int c, int t0, const unsigned char* mask, long* dest,
                       long dest_len, long n0, int* flag, void* stream);
 
+/* ---- the labels of every kept test segment of the segment-level evaluation (segment_eval.hip)
+ * scripts/run_eval_probs.py:27-57 (_get_extra_info), scripts/run_eval_probs.py:105-130, 155-158 (_load_test_data) ----
+ * x: the batch's full features fp32 [B][F][T], read in place; c: the channel of the WordHash feature; mask: reject_mask
+ * bytes [B] (non-zero = kept) or null.  rec (int32), wstart (fp64 seconds), subject_index / recording_index (int64): the
+ * epoch's arrays of n_index segments, the batch starts at `first`.  kinds: the event table of bm_segment_features ([R][NK]
+ * entries; word_kind: the slot of the word events); infos: [R] entries of bm_segment_eval_info_fill, one int64 array
+ * [n_words][3] = (word_index, sequence_id, segment_id) per recording.  For the kept rows in ascending order, rank r:
+ * dest[n0 + r][0 .. 7) = word_hash, word_index, sequence_id, segment_id, subject_index, recording_index, word_event.
+ *   word_hash  = the exact integer of the first non-zero of x[t0], x[t0 - 1] (only if t0 > 0), x[t0 + 1]
+ *                (scripts/run_eval_probs.py:116, 122-130); all zero is legal and stored as 0;
+ *   word_event = the last word event in table order with max(0, trunc(a)) <= t0 < min(T, trunc(b)), a = sr * (start -
+ *                wstart), b = a + sr * duration in fp64 (scripts/run_eval_probs.py:43-47), -1 without one; then
+ *                word_index = sequence_id = -1 and segment_id = 0, else the word-info row.
+ * *flag |= 1: the word hash is not finite, not an integer or |v| >= 2^63; 2: n0 + r reached dest_rows; 4: a recording
+ * index outside [0, R) (that row gets the no-word values).  ONE launch, a wavefront per row; no atomics on dest, one OR
+ * per workgroup that has a bit; the same bits on every run.  t0 < 0, t0 + 1 >= T, c outside [0, F) and n0 outside
+ * [0, dest_rows] are BM_ERR_ARG before any launch. */
+long bm_segment_eval_info_entry_bytes(void);
+int bm_segment_eval_info_fill(void* entry, const long* rows, long n);
+int bm_segment_eval_labels(const float* x, int B, int F, int T, int c, int t0, const unsigned char* mask,
+                           const int* rec, const double* wstart, const long* subject_index,
+                           const long* recording_index, long n_index, long first, const void* kinds, int NK,
+                           int word_kind, const void* infos, int R, double sr, long* dest, long dest_rows,
+                           long n0, int* flag, void* stream);
+/* The `seen_segment_hashes` loop of scripts/run_eval_probs.py:141-149 over a whole epoch: ids int64 [N] in [0, n_ids),
+ * first: int32 [n_ids] filled with INT_MAX by the caller.  Launch 1: atomicMin(&first[ids[i]], i); launch 2: mask[i] =
+ * (first[ids[i]] == i), first_row[i] = first[ids[i]].  An id out of range: *flag |= 8, mask 0, first_row -1.  N < 2^31. */
+int bm_first_occurrence(const long* ids, long N, long n_ids, int* first, unsigned char* mask, int* first_row,
+                        int* flag, void* stream);
+
 /* ---- fused Adam on the flat bucket (adam.hip)  torch.optim.Adam @ bm/train.py:118-119 ---- */
 int bm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, int step,
                  double lr, double beta1, double beta2, double eps, double grad_scale, void* stream);
