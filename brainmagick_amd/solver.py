@@ -4,8 +4,10 @@ CLIP loss -- the path BASELINE.json names -- or the L1 / MSE regression loss (bm
 FeatureDecodingLoss (bm/solver.py:81-86), and for the encode task (bm/solver.py:287-293) with the L1 / MSE loss; both
 with the optional low-pass filter of the MEG (`task.lowpass`, bm/solver.py:278-281) and the optional spectral penalty on
 the model's weights (`optim.svd`, bm/solver.py:379-380).
-Everything around it in the reference (flashy stages, checkpoint commit, tensorboard, dataset
-construction) stays the reference's business.
+The loop around it -- ``_run_one_epoch`` (bm/solver.py:325-401), ``train`` (bm/solver.py:189-228) with flashy's stages
+and checkpoint commit, ``restore`` (bm/solver.py:104-118) -- is ``train_loop.py``; ``run_epoch``, ``fit``, ``restore`` and
+``load_best`` here are pure dispatch onto it.  Tensorboard / wandb, Dora XPs, the hydra configuration and dataset
+construction from studies stay the reference's business.
 
 Differences to the reference, all MI355X-motivated and opt-in/neutral:
   * gradients / optimizer: ONE flat bucket -> reduce-scatter + fused Adam on the shard + all-gather
@@ -158,6 +160,18 @@ class Solver:
         self._flag_i = 0
         self._flag_ticket = None
         self._windows: tp.Dict[tuple, torch.Tensor] = {}      # (B, T, limit, device) -> bool [B, 1, T], t >= limit
+        # bm/solver.py:40,49-51 and flashy.BaseSolver.history: what ``fit`` keeps between epochs (train_loop.py)
+        self.history: tp.List[tp.Dict[str, dict]] = []
+        self.best_loss = float("inf")
+        self.best_epoch = 0
+        self.best_state: tp.Optional[dict] = None
+        self.last_test_epoch = 0
+        self.best_on = "device"                   # or "cpu": where ``best_state`` lives (a model not to be held twice)
+
+    @property
+    def epoch(self) -> int:
+        """flashy.BaseSolver.epoch: 1-based, the epoch that is running or will run next."""
+        return len(self.history) + 1
 
     # -- bm/solver.py:243 `batch.to(self.device)` ----------------------------------------------------
     def stage(self, batch):
@@ -573,10 +587,20 @@ class Solver:
 
     @torch.no_grad()
     def eval_step(self, batch) -> torch.Tensor:
+        loss = self._eval_loss(batch)
+        if loss is None:
+            raise RuntimeError("eval_step: every segment of the batch was rejected (a validation epoch, `run_epoch`, "
+                               "re-runs the last good batch in its place, bm/solver.py:345-352)")
+        return loss
+
+    def _eval_loss(self, batch) -> tp.Optional[torch.Tensor]:
+        """The body of ``eval_step`` (the caller holds ``no_grad``); None: the batch was fully rejected."""
         for m in self._all_models():
             m.train(False)
         self.loss.train(False)
         estimate, output, features_mask, _, limit = self._forward(batch, training=False)
+        if estimate is None:
+            return None
         if self.regression:
             loss = self.loss(estimate, output, self._loss_mask(features_mask, limit))
         else:
@@ -635,3 +659,30 @@ class Solver:
         segments, **kw)`` (``test_features``, ``used_names``, ``batch_size`` and `run_eval`'s settings)."""
         from . import retrieval
         return retrieval.segment_eval_epoch(self, segments, **kw)
+
+    # -- bm/solver.py:104-118, 189-228, 325-401: pure dispatch onto train_loop.py -------------------------------------
+    def run_epoch(self, loader, training: bool, *, max_batches: tp.Optional[int] = None,
+                  num_prints: int = 0) -> tp.Dict[str, float]:
+        """bm/solver.py:325-401 (``_run_one_epoch``): ``train_loop.run_epoch(self, loader, training, ...)``."""
+        from . import train_loop
+        return train_loop.run_epoch(self, loader, training, max_batches=max_batches, num_prints=num_prints)
+
+    def fit(self, train_loader, valid_loader, *, epochs: int, test: tp.Optional[tp.Callable[[], dict]] = None,
+            eval_every: int = 1, early_stop_patience: tp.Optional[int] = None, max_batches: tp.Optional[int] = None,
+            checkpoint=None, num_prints: int = 0) -> tp.List[tp.Dict[str, dict]]:
+        """bm/solver.py:189-228 (``train``): ``train_loop.fit(self, ...)``.  ``test``: a callable that returns the test
+        stage's metrics, e.g. ``lambda: solver.test_epoch(segments, **kw)``; it runs on the best state."""
+        from . import train_loop
+        return train_loop.fit(self, train_loader, valid_loader, epochs=epochs, test=test, eval_every=eval_every,
+                              early_stop_patience=early_stop_patience, max_batches=max_batches, checkpoint=checkpoint,
+                              num_prints=num_prints)
+
+    def restore(self, checkpoint, *, continue_from=None, continue_best: bool = True) -> bool:
+        """bm/solver.py:104-118: ``train_loop.restore(self, checkpoint, ...)``."""
+        from . import train_loop
+        return train_loop.restore(self, checkpoint, continue_from=continue_from, continue_best=continue_best)
+
+    def load_best(self) -> None:
+        """bm/solver.py:63-64: ``best_state`` into the models."""
+        from . import train_loop
+        train_loop.load_best(self)
