@@ -1,5 +1,5 @@
 // What the kernels that reduce over a workgroup, or over a grid in ONE launch, share: the scalar / 16-byte vector
-// instantiation of an element walk, the block maximum and sum, the ticket by which the workgroup that finishes last
+// instantiation of an element walk, the block maximum, sum and OR, the ticket by which the workgroup that finishes last
 // folds the others' partials, the workspace and LDS that go with it, and the fold of partial maxima into an amax slot.
 #pragma once
 #include "bm_common.h"
@@ -51,6 +51,19 @@ __device__ __forceinline__ float bm_block_sum(float v, float* sh) {
 template <int WAVES>
 __device__ __forceinline__ double bm_block_sum(double v, double* sh) {
     return bm_block_fold<WAVES>(bm_wave_sum_d(v), sh, [](double a, double b) { return a + b; });
+}
+// The OR of the wavefronts' flag bits in THREAD 0 only (another thread keeps `wv`): what a kernel does before thread 0
+// adds the workgroup's bits to a flag word in memory.  `wv`: bm_wave_or of the lanes' bits, or bits that are uniform over
+// the wavefront.  ONE barrier, in front of thread 0's reads of `sh`; an OR does not depend on the order.
+// (__lane_id() == 0 compiles to the test of bm_wave_to_lds, threadIdx.x & 63; spelled with threadIdx.x the compiler
+// also learns the low bits of threadIdx.x inside the branch, forms sh's address a second way, and word_hash_pick_kernel
+// holds both forms in registers across its loop: 2 VGPRs.)
+template <int WAVES>
+__device__ __forceinline__ int bm_block_or(int wv, int* sh) {
+    if (__lane_id() == 0) sh[threadIdx.x >> 6] = wv;
+    __syncthreads();
+    if (threadIdx.x == 0) wv = bm_pairwise<WAVES>(sh, [](int a, int b) { return a | b; });
+    return wv;
 }
 
 // ---- the last-arriver fold ----------------------------------------------------------------------------------------------

@@ -132,6 +132,11 @@ __device__ __forceinline__ double bm_wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+__device__ __forceinline__ int bm_wave_or(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
 // The step from a wavefront's value to a workgroup's: lane 0 of every wavefront puts it into sh[wavefront] (the block
 // reductions of bm_block.h are built on it).
 template <typename T>

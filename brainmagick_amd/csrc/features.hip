@@ -29,7 +29,7 @@
 //   1. two searches bound the window's candidates: events are sorted by start, so e.start < stop is a prefix
 //      [0, hi); the running maximum of start + duration is non-decreasing, so no event before lo = the first index whose
 //      running maximum reaches the window's start can overlap.  Every event of [lo, hi) is tested itself.  A search is
-//      a binary search widened to the wavefront: 64 probes per round (ft_lower_bound).
+//      a binary search widened to the wavefront: 64 probes per round (bm_events_lower_bound).
 //   2. FT_THREADS candidates at a time: thread i computes the paint range of candidate i into LDS; then every thread
 //      walks the candidates IN ORDER and records the last one that paints each of ITS window samples (thread t owns the
 //      samples t, t + FT_THREADS, ...: one writer per sample, so "the later event wins" needs no atomic and has one
@@ -47,7 +47,7 @@
 // latency of a workgroup's chain of dependent loads (segment -> tables -> searches -> candidates -> event -> array), not
 // bandwidth: hence the wavefront-wide searches and the FT_ILP loads in flight per lane.  A lane owns samples t, t + 256:
 // at T = 361 the second round runs 105 of 256 lanes.
-#include "bm_common.h"
+#include "bm_events.h"
 
 #pragma clang fp contract(off)
 
@@ -59,12 +59,6 @@
 
 enum { FT_CONSTANT = 0, FT_RESAMPLED = 1, FT_CHUNK = 2 };
 
-struct FtKind {                     // one event kind of one recording; start is non-decreasing
-    const double* start;
-    const double* dur;
-    const double* runmax;           // runmax[i] = max over j <= i of start[j] + dur[j]
-    long n;
-};
 struct FtSrc {                      // one feature of one recording
     const void* data;               // constant: float [n][dim]; resampled / chunk: FtArr [n]
 };
@@ -82,7 +76,7 @@ struct FtPlan {
 };
 
 extern "C" long bm_features_table_entry_bytes(int which) {
-    return which == 0 ? (long)sizeof(FtKind) : which == 1 ? (long)sizeof(FtSrc) : which == 2 ? (long)sizeof(FtArr) : -1L;
+    return which == 0 ? (long)sizeof(BmEventKind) : which == 1 ? (long)sizeof(FtSrc) : which == 2 ? (long)sizeof(FtArr) : -1L;
 }
 
 extern "C" int bm_features_kind_fill(void* entry, const double* start, const double* dur, const double* runmax, long n) {
@@ -90,7 +84,7 @@ extern "C" int bm_features_kind_fill(void* entry, const double* start, const dou
                "features table: bad event kind (%ld events)", n);
     BM_REQUIRE((((uintptr_t)start | (uintptr_t)dur | (uintptr_t)runmax) & 7) == 0,
                "features table: the event times are not 8-byte aligned");
-    FtKind* e = (FtKind*)entry;
+    BmEventKind* e = (BmEventKind*)entry;
     e->start = start;
     e->dur = dur;
     e->runmax = runmax;
@@ -113,26 +107,6 @@ extern "C" int bm_features_array_fill(void* entry, const float* base, long L, do
     e->L = L;
     e->er = er;
     return BM_OK;
-}
-
-// First index of the non-decreasing x[0 .. n) with x[i] >= v (n when there is none), found by a whole wavefront: its 64
-// lanes probe 64 evenly spaced elements per round, so a table of n events costs ceil(log64 n) dependent loads where a
-// binary search costs log2 n (a window's prologue is a chain of dependent loads: its latency, not its bandwidth, is what
-// a workgroup waits for).  Every lane returns the same index.
-__device__ __forceinline__ int ft_lower_bound(const double* __restrict__ x, int n, double v) {
-    const int lane = threadIdx.x & (BM_WAVE - 1);
-    int lo = 0, hi = n;                                     // the answer lies in [lo, hi]
-    while (lo < hi) {
-        const int step = (hi - lo + BM_WAVE - 1) / BM_WAVE;
-        const int idx = lo + lane * step;
-        const bool ge = idx < hi ? x[idx] >= v : true;
-        const unsigned long long hit = __ballot(ge);
-        const int first = hit ? __ffsll((long long)hit) - 1 : BM_WAVE;        // probes before `first` are below v
-        const int base = lo;
-        lo = first == 0 ? base : base + (first - 1) * step + 1;
-        hi = min(hi, base + first * step);
-    }
-    return lo;
 }
 
 struct FtOverlap {
@@ -195,7 +169,7 @@ __device__ __forceinline__ long ft_column(int rule, const FtOverlap& ov, double 
 }
 
 __global__ __launch_bounds__(FT_THREADS) void segment_features_kernel(
-    const FtPlan plan, int NF, int NK, int mask_kind, const FtKind* __restrict__ kinds, const FtSrc* __restrict__ srcs,
+    const FtPlan plan, int NF, int NK, int mask_kind, const BmEventKind* __restrict__ kinds, const FtSrc* __restrict__ srcs,
     int R, const int* __restrict__ rec, const double* __restrict__ wstart, const double* __restrict__ wdur, int F, int T, double sr, float* __restrict__ dst, unsigned char* __restrict__ mask, int* flag) {
     __shared__ int owner[FT_TMAX];
     __shared__ int cw0[FT_THREADS];
@@ -222,13 +196,13 @@ __global__ __launch_bounds__(FT_THREADS) void segment_features_kernel(
 
         // 1 + 2: the last event of the kind that paints each window sample (-1: none)
         for (int w = tid; w < T; w += FT_THREADS) owner[w] = -1;
-        FtKind K;
+        BmEventKind K;
         K.start = K.dur = K.runmax = nullptr;
         K.n = 0;
         if (valid) K = kinds[(long)r * NK + k];
         if (K.n > 0) {
-            const int hi = ft_lower_bound(K.start, (int)K.n, wstop);          // n < 2^30: bm_features_kind_fill
-            const int lo = ft_lower_bound(K.runmax, (int)K.n, ws);
+            const int hi = bm_events_lower_bound(K.start, (int)K.n, wstop);   // n < 2^30: bm_features_kind_fill
+            const int lo = bm_events_lower_bound(K.runmax, (int)K.n, ws);
             for (int base = lo; base < hi; base += FT_THREADS) {
                 __syncthreads();                                        // the previous chunk has been read
                 const int e = base + tid;
@@ -347,7 +321,7 @@ extern "C" int bm_segment_features(const int* feat_table, const float* feat_defa
                "segment_features: dst is not 4-byte aligned, or the window times are not 8-byte aligned");
     const int slabs = F > 0 ? cdiv(F, FT_SLAB) : 1;
     hipLaunchKernelGGL(segment_features_kernel, dim3(slabs, B), dim3(FT_THREADS), 0, (hipStream_t)stream, plan, NF, NK,
-                       mask_kind, (const FtKind*)kinds, (const FtSrc*)srcs, R, rec + first, wstart + first, wdur + first, F, T, sr, dst,
+                       mask_kind, (const BmEventKind*)kinds, (const FtSrc*)srcs, R, rec + first, wstart + first, wdur + first, F, T, sr, dst,
                        mask, flag);
     return bm_check_launch("segment_features");
 }

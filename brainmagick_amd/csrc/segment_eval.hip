@@ -3,11 +3,9 @@
 //
 // bm_segment_eval_labels -- for the kept rows of a batch in ascending order, rank r: dest[n0 + r][0 .. 7) =
 //     word_hash, word_index, sequence_id, segment_id, subject_index, recording_index, word_event        (int64)
-//   word_hash   the first non-zero of x[t0], x[t0 - 1] (only if t0 > 0), x[t0 + 1] of the WordHash channel: the chain of
-//               torch.where(wh == 0, ..., wh) of :122-130 (reach 1; bm/wer.py has reach 2).  -0.0 counts as zero, a NaN
-//               does not.  All zero is legal (the assert of :131 is commented out) and stored as 0.  Stored as the exact
-//               integer of the fp32 value; not finite, not an integer or |v| >= 2^63 raises bit 1 (0, or the value
-//               truncated towards zero, is stored).
+//   word_hash   the word-label rule of bm_events.h with a reach of 1 sample (:122-130; bm/wer.py has reach 2).  All zero
+//               is legal (the assert of :131 is commented out) and stored as 0; a value that is no legal label raises
+//               bit 1.
 //   word_event  the index, in the recording's word table, of the LAST word event in table order that covers column t0
 //               by the arithmetic of _get_extra_info (:43-47), in fp64 and uncontracted:
 //                   a = sr * (ev.start - wstart);  b = a + sr * ev.duration;
@@ -47,7 +45,8 @@
 // first_row -1.
 #include <climits>
 
-#include "bm_common.h"
+#include "bm_block.h"
+#include "bm_events.h"
 
 #pragma clang fp contract(off)
 
@@ -55,18 +54,10 @@
 #define SE_WAVES (SE_THREADS / BM_WAVE)
 #define SE_COLS 7
 
-struct SeKind {                     // FtKind of features.hip: one event kind of one recording, start non-decreasing
-    const double* start;
-    const double* dur;
-    const double* runmax;
-    long n;
-};
 struct SeInfo {                     // one recording's word info [n][3] int64: word_index, sequence_id, segment_id
     const long* rows;
     long n;
 };
-
-extern "C" long bm_features_table_entry_bytes(int which);
 
 extern "C" long bm_segment_eval_info_entry_bytes(void) { return (long)sizeof(SeInfo); }
 
@@ -79,26 +70,10 @@ extern "C" int bm_segment_eval_info_fill(void* entry, const long* rows, long n) 
     return BM_OK;
 }
 
-// ft_lower_bound of features.hip: first index of the non-decreasing x[0 .. n) with x[i] >= v, by a whole wavefront.
-__device__ __forceinline__ int se_lower_bound(const double* __restrict__ x, int n, double v, int lane) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int step = (hi - lo + BM_WAVE - 1) / BM_WAVE;
-        const int idx = lo + lane * step;
-        const bool ge = idx < hi ? x[idx] >= v : true;
-        const unsigned long long hit = __ballot(ge);
-        const int first = hit ? __ffsll((long long)hit) - 1 : BM_WAVE;
-        const int base = lo;
-        lo = first == 0 ? base : base + (first - 1) * step + 1;
-        hi = min(hi, base + first * step);
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(SE_THREADS) void segment_eval_labels_kernel(
     const float* __restrict__ x, long row_stride, long offset, int t0, int T, const unsigned char* __restrict__ mask, int B,
     const int* __restrict__ rec, const double* __restrict__ wstart, const long* __restrict__ subject,
-    const long* __restrict__ recording, const SeKind* __restrict__ kinds, int NK, int word_kind,
+    const long* __restrict__ recording, const BmEventKind* __restrict__ kinds, int NK, int word_kind,
     const SeInfo* __restrict__ infos, int R, double sr, double reach_hi, double reach_lo, long* __restrict__ dest,
     long dest_rows, long n0, int* flag) {
     __shared__ int wave_n[SE_WAVES];
@@ -125,25 +100,14 @@ __global__ __launch_bounds__(SE_THREADS) void segment_eval_labels_kernel(
     int bits = 0;
     if (keep) {
         const float* p = x + (long)b * row_stride + offset;              // &x[b][c][t0]; the host checked 0 <= t0, t0 + 1 < T
-        float v = p[0];
-        const float m1 = t0 > 0 ? p[-1] : 0.f, p1 = p[1];
-        if (v == 0.f && t0 > 0) v = m1;
-        if (v == 0.f) v = p1;
-        long hash = 0;
-        if (v == 0.f) {
-            hash = 0;
-        } else if (!(fabsf(v) < 9223372036854775808.f)) {                // NaN, +-inf, |v| >= 2^63
-            bits |= 1;
-        } else {
-            hash = (long)v;
-            if (truncf(v) != v) bits |= 1;
-        }
+        const BmWordLabel w = bm_word_label_classify(bm_word_label_pick<1>(p, t0));
+        if (w.is_illegal) bits |= 1;
 
         const int r = rec[b];
         const bool valid = (unsigned)r < (unsigned)R;
         if (!valid) bits |= 4;
         long event = -1;
-        SeKind K;
+        BmEventKind K;
         K.start = K.dur = K.runmax = nullptr;
         K.n = 0;
         SeInfo I;
@@ -156,8 +120,8 @@ __global__ __launch_bounds__(SE_THREADS) void segment_eval_labels_kernel(
         const int n = (int)(K.n < I.n ? K.n : I.n);                      // < 2^30: the fills; equal on checked tables
         if (n > 0) {
             const double ws = wstart[b];
-            const int hi = se_lower_bound(K.start, n, ws + reach_hi, lane);
-            const int lo = se_lower_bound(K.runmax, n, ws + reach_lo, lane);
+            const int hi = bm_events_lower_bound(K.start, n, ws + reach_hi);
+            const int lo = bm_events_lower_bound(K.runmax, n, ws + reach_lo);
             for (int top = hi; top > lo; top -= BM_WAVE) {
                 const int e = top - 1 - lane;                            // lane 0 tests the last candidate
                 bool covered = false;
@@ -180,7 +144,7 @@ __global__ __launch_bounds__(SE_THREADS) void segment_eval_labels_kernel(
             if (lane < SE_COLS) {
                 long value;
                 if (lane == 0)
-                    value = hash;
+                    value = w.label;
                 else if (lane <= 3)
                     value = event >= 0 ? I.rows[event * 3 + (lane - 1)] : (lane == 3 ? 0L : -1L);
                 else if (lane == 4)
@@ -195,14 +159,8 @@ __global__ __launch_bounds__(SE_THREADS) void segment_eval_labels_kernel(
             bits |= 2;
         }
     }
-    if (lane == 0) wave_bits[wave] = bits;                               // uniform over the wavefront
-    __syncthreads();
-    if (tid == 0) {
-        int all = 0;
-#pragma unroll
-        for (int w = 0; w < SE_WAVES; ++w) all |= wave_bits[w];
-        if (all) atomicOr(flag, all);
-    }
+    const int all = bm_block_or<SE_WAVES>(bits, wave_bits);          // bits: uniform over the wavefront
+    if (tid == 0 && all) atomicOr(flag, all);
 }
 
 extern "C" int bm_segment_eval_labels(const float* x, int B, int F, int T, int c, int t0, const unsigned char* mask,
@@ -218,7 +176,6 @@ extern "C" int bm_segment_eval_labels(const float* x, int B, int F, int T, int c
     BM_REQUIRE(sr > 0.0 && sr < 1e12, "segment_eval_labels: sample rate %g", sr);
     BM_REQUIRE(first >= 0 && first + B <= n_index, "segment_eval_labels: segments [%ld, %ld) of %ld", first, first + B, n_index);
     BM_REQUIRE(n0 >= 0 && dest_rows >= 0 && n0 <= dest_rows, "segment_eval_labels: first row %ld of %ld", n0, dest_rows);
-    BM_REQUIRE(bm_features_table_entry_bytes(0) == (long)sizeof(SeKind), "segment_eval_labels: the event table's entry changed");
     if (B == 0) return BM_OK;
     BM_REQUIRE(x && dest && flag && rec && wstart && subject_index && recording_index && (R == 0 || (kinds && infos)),
                "segment_eval_labels: null pointer");
@@ -227,7 +184,7 @@ extern "C" int bm_segment_eval_labels(const float* x, int B, int F, int T, int c
                "segment_eval_labels: misaligned pointer");
     hipLaunchKernelGGL(segment_eval_labels_kernel, dim3(cdiv(B, SE_WAVES)), dim3(SE_THREADS), 0, (hipStream_t)stream, x,
                        (long)F * T, (long)c * T + t0, t0, T, mask, B, rec + first, wstart + first, subject_index + first,
-                       recording_index + first, (const SeKind*)kinds, NK, word_kind, (const SeInfo*)infos, R, sr,
+                       recording_index + first, (const BmEventKind*)kinds, NK, word_kind, (const SeInfo*)infos, R, sr,
                        (t0 + 2) / sr, (t0 - 1) / sr, dest, dest_rows, n0, flag);
     return bm_check_launch("segment_eval_labels");
 }
@@ -258,16 +215,8 @@ __global__ __launch_bounds__(SE_THREADS) void first_occurrence_mask_kernel(const
         mask[i] = f == i ? 1 : 0;
         first_row[i] = f;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bits |= __shfl_xor(bits, o);
-    if ((tid & (BM_WAVE - 1)) == 0) wave_bits[tid >> 6] = bits;
-    __syncthreads();
-    if (tid == 0) {
-        int all = 0;
-#pragma unroll
-        for (int w = 0; w < SE_WAVES; ++w) all |= wave_bits[w];
-        if (all) atomicOr(flag, all);
-    }
+    const int all = bm_block_or<SE_WAVES>(bm_wave_or(bits), wave_bits);
+    if (tid == 0 && all) atomicOr(flag, all);
 }
 
 extern "C" int bm_first_occurrence(const long* ids, long N, long n_ids, int* first, unsigned char* mask, int* first_row,

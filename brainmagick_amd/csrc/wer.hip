@@ -3,9 +3,7 @@
 //     x      = the batch's full features [B][F][T] fp32, read in place (channel c = the WordHash feature)
 //     mask   = reject_mask [B] bytes (true = the segment was kept), or null: every row is kept
 //     dest[n0 + r] = label of the kept row of rank r, rows in ascending order: the order of `word_hash[reject_mask]`
-// The label is the first non-zero of x[t0], x[t0 - 1] (only if t0 > 0), x[t0 + 1], x[t0 - 2] (only if t0 > 1),
-// x[t0 + 2] -- the chain of torch.where(wh == 0, ..., wh) of bm/wer.py:58-64 with its two guards: -0.0 counts as zero
-// and a NaN does not, as `wh == 0` decides.  It is stored as the exact integer of the fp32 value (int64).
+// The label is the word-label rule of bm_events.h with a reach of 2 samples (bm/wer.py:58-64).
 //
 // Flag word (one int32, owned by retrieval.py -- not the Solver's):
 //     1  every candidate of a kept row is zero (the reference's `assert (wh != 0).all()`, bm/wer.py:65); dest gets 0
@@ -21,7 +19,8 @@
 // and stored by lane 0 alone -- the launch is the word's only writer on its stream.  Two runs give the same bits.
 // A batch is a few hundred rows and the launch reads 5 floats and a byte per row: it is launch latency, and one
 // workgroup keeps it free of a second pass or a cross-workgroup scan.
-#include "bm_common.h"
+#include "bm_block.h"
+#include "bm_events.h"
 
 #define WH_THREADS 256
 #define WH_WAVES (WH_THREADS / BM_WAVE)
@@ -52,41 +51,19 @@ __global__ __launch_bounds__(WH_THREADS) void word_hash_pick_kernel(const float*
         }
         if (keep) {
             const float* p = x + (long)b * row_stride + offset;       // &x[b][c][t0]; the host checked 0 <= t0, t0 + 2 < T
-            float v = p[0];
-            const float m1 = t0 > 0 ? p[-1] : 0.f, p1 = p[1];
-            const float m2 = t0 > 1 ? p[-2] : 0.f, p2 = p[2];
-            if (v == 0.f && t0 > 0) v = m1;
-            if (v == 0.f) v = p1;
-            if (v == 0.f && t0 > 1) v = m2;
-            if (v == 0.f) v = p2;
-            long label = 0;
-            if (v == 0.f) {
-                bits |= 1;
-            } else if (!(fabsf(v) < 9223372036854775808.f)) {         // NaN, +-inf, |v| >= 2^63
-                bits |= 2;
-            } else {
-                label = (long)v;
-                if (truncf(v) != v) bits |= 2;
-            }
+            const BmWordLabel w = bm_word_label_classify(bm_word_label_pick<2>(p, t0));
+            bits |= w.is_zero ? 1 : w.is_illegal ? 2 : 0;
             const long r = base + before + __popcll(kept & ((1ull << lane) - 1ull));
             if (r < dest_len)
-                dest[r] = label;
+                dest[r] = w.label;
             else
                 bits |= 4;
         }
         base += total;
         __syncthreads();                                              // wave_n is rewritten by the next stride
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bits |= __shfl_xor(bits, o);
-    if (lane == 0) wave_bits[wave] = bits;
-    __syncthreads();
-    if (tid == 0) {
-        int all = 0;
-#pragma unroll
-        for (int w = 0; w < WH_WAVES; ++w) all |= wave_bits[w];
-        if (all) *flag = *flag | all;
-    }
+    const int all = bm_block_or<WH_WAVES>(bm_wave_or(bits), wave_bits);
+    if (tid == 0 && all) *flag = *flag | all;
 }
 
 extern "C" int bm_word_hash_pick(const float* x, int B, int F, int T, int c, int t0, const unsigned char* mask,

@@ -109,24 +109,12 @@ def window_samples(sample_rate: float, tmin: float, tmax: float, baseline=(None,
 
 # One flag word per device, owned by this module (NOT the Solver's index_error_flag): raised by the gather kernel when a
 # segment is out of range, read once per epoch by the loader.
-_range_flags: tp.Dict[torch.device, torch.Tensor] = {}
-
-
-def range_error_flag(device) -> torch.Tensor:
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    flag = _range_flags.get(device)
-    if flag is None:
-        flag = _range_flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
-    return flag
+range_error_flag = H.DeviceFlag()
 
 
 def raise_if_range_error(device) -> None:
     """Synchronising check of the flag, which it clears."""
-    flag = range_error_flag(device)
-    if int(flag.item()) != 0:
-        flag.zero_()
+    if range_error_flag.take(device):
         raise IndexError("a segment's recording or first sample is out of range (such segments were gathered as zeros)")
 
 

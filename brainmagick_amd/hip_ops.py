@@ -542,36 +542,51 @@ def conv_strided_wgrad(a: torch.Tensor, xl: torch.Tensor, KS: int, stride: int, 
     return out
 
 
+class DeviceFlag:
+    """A word of flag bits per device that kernels raise and the host reads at a synchronisation point of its choosing:
+    ``n_words`` int32, zero when first asked for.  Every owner (this module's index flag, the dataset's range flag, the
+    two test epochs' label flags) is ONE instance: the words of two owners are never the same memory."""
+
+    def __init__(self, n_words: int = 1):
+        self.n_words = n_words
+        self._words: tp.Dict[torch.device, torch.Tensor] = {}
+
+    def __call__(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        flag = self._words.get(device)
+        if flag is None:
+            flag = self._words[device] = torch.zeros(self.n_words, device=device, dtype=torch.int32)
+        return flag
+
+    def take(self, device=None, word: int = 0) -> int:
+        """Synchronising: the bits of ``word``, which it clears when any is set (the other words stay).  ``device=None``:
+        of the first device, among those that have the flag, on which any is set."""
+        for flag in (list(self._words.values()) if device is None else [self(device)]):
+            bits = int(flag[word].item())
+            if bits:
+                flag[word:word + 1].zero_()
+                return bits
+        return 0
+
+
 # Device-side "index out of range" flag (one int32 per device).  The grouped kernels never read outside
 # their weight tables (bad indices are clamped to group 0 by bm_index_to_i32 / skipped by
 # bm_group_by_index); the flag is raised as an IndexError at the next synchronisation point the caller
 # chooses (`raise_if_index_error`, called by Solver next to the reference's isfinite asserts), or
 # immediately with BM_CHECK_INDICES=1.
-_index_err: tp.Dict[torch.device, torch.Tensor] = {}
+# Three words: [index out of range, non-finite input, loss mask bits: 1 = ClipLoss mask not all-true, NO_MASK_BIT,
+# CATEGORY_RANGE_BIT]
+index_error_flag = DeviceFlag(3)
 _CHECK_INDICES_NOW = _os.environ.get("BM_CHECK_INDICES", "0") == "1"
-
-
-def index_error_flag(device) -> torch.Tensor:
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    flag = _index_err.get(device)
-    if flag is None:
-        # [index out of range, non-finite input, loss mask bits: 1 = ClipLoss mask not all-true, NO_MASK_BIT,
-        # CATEGORY_RANGE_BIT]
-        flag = torch.zeros(3, device=device, dtype=torch.int32)
-        _index_err[device] = flag
-    return flag
 
 
 def raise_if_index_error(device=None):
     """Synchronising check of the flag; raises like the reference's out-of-range gather would."""
-    flags = list(_index_err.values()) if device is None else [index_error_flag(device)]
-    for flag in flags:
-        if int(flag[0].item()) != 0:
-            flag[0:1].zero_()       # (the other two words -- non-finite input, bad mask -- belong to the Solver)
-            raise IndexError("subject / layout index out of range for the weight table "
-                             "(bm/models/common.py:57 would raise in `weights.gather`)")
+    if index_error_flag.take(device):       # (the other two words -- non-finite input, bad mask -- belong to the Solver)
+        raise IndexError("subject / layout index out of range for the weight table "
+                         "(bm/models/common.py:57 would raise in `weights.gather`)")
 
 
 def index_i32(idx: torch.Tensor, G: int) -> torch.Tensor:
@@ -2239,6 +2254,44 @@ WORD_HASH_VALUE_BIT = 2         # the chosen value is not finite, not an integer
 WORD_HASH_DEST_BIT = 4          # a kept row had no element of dest left
 
 
+def _labels_shape_check(name: str, reach: int, cite: str, cols: tp.Optional[int], shape: tp.Sequence[int], c: int,
+                        check_at_time: int, dest, n0: int, count: tp.Optional[int]) -> None:
+    """The shape checks of the two label launches (``word_hash_pick``: ``reach`` 2, ``dest`` = its number of labels,
+    ``cols`` None; ``segment_eval_labels``: ``reach`` 1, ``dest`` = its shape, ``[rows, cols]``), in one order: the
+    features, ``check_at_time`` (``cite``: the reference's lines that would wrap around), the channel, the shape of
+    ``dest``, ``count``, the room in ``dest``."""
+    if len(shape) != 3:
+        raise ValueError(f"{name}: the features are {tuple(shape)}, expected [B, F_all, T]")
+    B, F, T = (int(s) for s in shape)
+    if check_at_time < 0 or check_at_time + reach >= T:
+        raise ValueError(f"{name}: check_at_time = {check_at_time} reads the samples {check_at_time - reach} .. "
+                         f"{check_at_time + reach} of a window of {T} ({cite} would wrap around or raise IndexError)")
+    if not 0 <= c < F:
+        raise ValueError(f"{name}: channel {c} of {F}")
+    rows, unit = dest, "labels"
+    if cols is not None:
+        if len(dest) != 2 or int(dest[1]) != cols:
+            raise ValueError(f"{name}: dest is {tuple(dest)}, expected [rows, {cols}]")
+        rows, unit = int(dest[0]), "rows"
+    count = B if count is None else int(count)
+    if not 0 <= count <= B:
+        raise ValueError(f"{name}: {count} kept rows of a batch of {B}")
+    if n0 < 0 or n0 + count > rows:
+        raise ValueError(f"{name}: dest holds {rows} {unit}, the batch writes {n0} .. {n0 + count - 1}")
+
+
+def _labels_tensor_check(name: str, features: torch.Tensor, dest: torch.Tensor, flag: torch.Tensor,
+                         reject_mask: tp.Optional[torch.Tensor]) -> None:
+    """What the two label launches ask of their tensors, behind the shape checks."""
+    _req(features, f"{name}.features")
+    _req(dest, f"{name}.dest", torch.int64)
+    _req(flag, f"{name}.flag", torch.int32)
+    if reject_mask is not None:
+        _req(reject_mask, f"{name}.reject_mask", torch.bool)
+        if reject_mask.shape != (features.shape[0],):
+            raise ValueError(f"{name}: reject_mask is {tuple(reject_mask.shape)} for a batch of {features.shape[0]}")
+
+
 def word_hash_pick_check(shape: tp.Sequence[int], c: int, check_at_time: int, n_dest: int, n0: int = 0,
                          count: tp.Optional[int] = None) -> None:
     """The ``ValueError``s of ``word_hash_pick``, from the shapes alone (nothing is launched, no tensor is touched):
@@ -2246,19 +2299,7 @@ def word_hash_pick_check(shape: tp.Sequence[int], c: int, check_at_time: int, n_
     ``word_hash[:, check_at_time + 2]`` would wrap around or raise ``IndexError``); ``c`` outside ``[0, F_all)``; a
     negative ``n0``; a ``dest`` with fewer than ``n0 + count`` elements (``count``: the kept rows when the caller knows
     them, else all ``B``)."""
-    if len(shape) != 3:
-        raise ValueError(f"word_hash_pick: the features are {tuple(shape)}, expected [B, F_all, T]")
-    B, F, T = (int(s) for s in shape)
-    if check_at_time < 0 or check_at_time + 2 >= T:
-        raise ValueError(f"word_hash_pick: check_at_time = {check_at_time} reads the samples {check_at_time - 2} .. "
-                         f"{check_at_time + 2} of a window of {T} (bm/wer.py:58-64 would wrap around or raise IndexError)")
-    if not 0 <= c < F:
-        raise ValueError(f"word_hash_pick: channel {c} of {F}")
-    count = B if count is None else int(count)
-    if not 0 <= count <= B:
-        raise ValueError(f"word_hash_pick: {count} kept rows of a batch of {B}")
-    if n0 < 0 or n0 + count > n_dest:
-        raise ValueError(f"word_hash_pick: dest holds {n_dest} labels, the batch writes {n0} .. {n0 + count - 1}")
+    _labels_shape_check("word_hash_pick", 2, "bm/wer.py:58-64", None, shape, c, check_at_time, n_dest, n0, count)
 
 
 def word_hash_pick(features: torch.Tensor, c: int, check_at_time: int, reject_mask: tp.Optional[torch.Tensor],
@@ -2273,14 +2314,8 @@ def word_hash_pick(features: torch.Tensor, c: int, check_at_time: int, reject_ma
     if not isinstance(features, torch.Tensor) or not isinstance(dest, torch.Tensor):
         raise BmHipError("word_hash_pick: features and dest are tensors")
     word_hash_pick_check(features.shape, c, check_at_time, dest.numel(), n0, count)
-    _req(features, "word_hash_pick.features")
-    _req(dest, "word_hash_pick.dest", torch.int64)
-    _req(flag, "word_hash_pick.flag", torch.int32)
+    _labels_tensor_check("word_hash_pick", features, dest, flag, reject_mask)
     B, F, T = features.shape
-    if reject_mask is not None:
-        _req(reject_mask, "word_hash_pick.reject_mask", torch.bool)
-        if reject_mask.shape != (B,):
-            raise ValueError(f"word_hash_pick: reject_mask is {tuple(reject_mask.shape)} for a batch of {B}")
     if dest.dim() != 1 or flag.numel() < 1:
         raise ValueError("word_hash_pick: dest is one-dimensional and the flag holds one word")
 
@@ -2342,23 +2377,8 @@ def segment_eval_labels_check(shape: tp.Sequence[int], c: int, check_at_time: in
     reference's ``word_hash[:, check_at_time + 1]`` would wrap around or raise ``IndexError``); ``c`` outside
     ``[0, F_all)``; a ``dest`` that is not ``[rows, 7]``; a negative ``n0``; fewer than ``n0 + count`` rows (``count``:
     the kept rows when the caller knows them, else all ``B``)."""
-    if len(shape) != 3:
-        raise ValueError(f"segment_eval_labels: the features are {tuple(shape)}, expected [B, F_all, T]")
-    B, F, T = (int(s) for s in shape)
-    if check_at_time < 0 or check_at_time + 1 >= T:
-        raise ValueError(f"segment_eval_labels: check_at_time = {check_at_time} reads the samples {check_at_time - 1} .. "
-                         f"{check_at_time + 1} of a window of {T} (scripts/run_eval_probs.py:116-130 would wrap around "
-                         "or raise IndexError)")
-    if not 0 <= c < F:
-        raise ValueError(f"segment_eval_labels: channel {c} of {F}")
-    if len(dest_shape) != 2 or int(dest_shape[1]) != len(SEGMENT_EVAL_COLUMNS):
-        raise ValueError(f"segment_eval_labels: dest is {tuple(dest_shape)}, expected [rows, {len(SEGMENT_EVAL_COLUMNS)}]")
-    count = B if count is None else int(count)
-    if not 0 <= count <= B:
-        raise ValueError(f"segment_eval_labels: {count} kept rows of a batch of {B}")
-    if n0 < 0 or n0 + count > int(dest_shape[0]):
-        raise ValueError(f"segment_eval_labels: dest holds {int(dest_shape[0])} rows, the batch writes {n0} .. "
-                         f"{n0 + count - 1}")
+    _labels_shape_check("segment_eval_labels", 1, "scripts/run_eval_probs.py:116-130", len(SEGMENT_EVAL_COLUMNS), shape, c,
+                        check_at_time, dest_shape, n0, count)
 
 
 def segment_eval_labels(features: torch.Tensor, c: int, check_at_time: int, reject_mask: tp.Optional[torch.Tensor],
@@ -2383,14 +2403,8 @@ def segment_eval_labels(features: torch.Tensor, c: int, check_at_time: int, reje
         raise ValueError(f"segment_eval_labels: the word kind {word_kind} of {events.n_kinds} event kinds")
     if len(infos) != len(events):
         raise ValueError(f"segment_eval_labels: word information for {len(infos)} recordings, events for {len(events)}")
-    _req(features, "segment_eval_labels.features")
-    _req(dest, "segment_eval_labels.dest", torch.int64)
-    _req(flag, "segment_eval_labels.flag", torch.int32)
+    _labels_tensor_check("segment_eval_labels", features, dest, flag, reject_mask)
     B, F, T = features.shape
-    if reject_mask is not None:
-        _req(reject_mask, "segment_eval_labels.reject_mask", torch.bool)
-        if reject_mask.shape != (B,):
-            raise ValueError(f"segment_eval_labels: reject_mask is {tuple(reject_mask.shape)} for a batch of {B}")
     rec, wstart = arrays["rec"], arrays["wstart"]
     subject, recording = arrays["subject_index"], arrays["recording_index"]
     _req(rec, "segment_eval_labels.rec", torch.int32)

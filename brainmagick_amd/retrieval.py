@@ -153,25 +153,12 @@ def get_wer(clip: ClipLoss, estimates: torch.Tensor, outputs: torch.Tensor, word
 
 # One flag word per device for the word labels (hip_ops.WORD_HASH_*_BIT), owned by this module like the dataset's
 # range flag -- NOT the Solver's flag word.  Read once per test epoch, after the last batch.
-_word_hash_flags: tp.Dict[torch.device, torch.Tensor] = {}
-
-
-def word_hash_flag(device) -> torch.Tensor:
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    flag = _word_hash_flags.get(device)
-    if flag is None:
-        flag = _word_hash_flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
-    return flag
+word_hash_flag = H.DeviceFlag()
 
 
 def raise_if_word_hash_error(device) -> None:
     """Synchronising check of the flag, which it clears."""
-    flag = word_hash_flag(device)
-    bits = int(flag.item())
-    if bits:
-        flag.zero_()
+    bits = word_hash_flag.take(device)
     if bits & H.WORD_HASH_ALL_ZERO_BIT:
         raise AssertionError("assert (wh != 0).all() (bm/wer.py:65): a kept segment has no word hash at check_at_time, "
                              "one or two samples around it")
@@ -205,20 +192,23 @@ def _free_bytes(device) -> int:
     return int(free) + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
-def collect_wer(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str],
-                check_at_time: int) -> tp.Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """bm/wer.py:24-25, 47-69, the collection loop: ``(estimates [n, ...], outputs [n, ...], word_hashes [n] int64)`` of
-    the kept segments of ``loader``'s device batches (at most ``total`` segments), all three views of resident device
-    arrays.  See ``wer_epoch``, which builds the loader."""
+def _collect(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str], *, name: str,
+             label_cols: tp.Tuple[int, ...], flag: "H.DeviceFlag", launch: tp.Callable[..., None], what: str, cite: str):
+    """The collection loop of both test epochs: ``(estimates [n, ...], outputs [n, ...], labels [n, *label_cols]
+    int64)`` of the kept segments of ``loader``'s device batches (at most ``total`` segments), views of resident device
+    arrays that are allocated at the first kept batch's row shape.  Under ``no_grad`` and in eval mode, per batch:
+    ``solver._process_batch`` on the batch with the extracted features; a fully rejected batch is skipped; estimate and
+    output are copied in at the running row count ``n``, and ``launch(batch, k, reject_mask, labels, n, m)`` writes the
+    labels of batch ``k``'s ``m`` kept rows from ``labels[n]`` on.  ``flag``'s word is cleared before the first launch
+    (bits an epoch that ended in an exception left behind) and left to the caller to read.  ``name``: "wer" or
+    "segment_eval", for the errors; ``what`` / ``cite``: the two texts that differ."""
+    from .solver import Solver
     used_names = list(used_names)
-    channel = test_features.get_slice("WordHash").start
-    for model in solver._all_models():
-        model.train(False)
-    solver.loss.train(False)
-    estimates = outputs = hashes = flag = None
+    Solver._eval_mode(solver)                               # unbound: any solver that has ``_all_models`` and ``loss``
+    estimates = outputs = labels = None
     n = 0
     with torch.no_grad():
-        for batch in loader:
+        for k, batch in enumerate(loader):
             features = test_features.extract_features(batch.features, used_names)
             estimate, output, _, reject_mask = solver._process_batch(batch.replace(features=features))
             if getattr(solver, "_gather", None) is not None and solver.feature_model is None:
@@ -227,29 +217,42 @@ def collect_wer(solver, loader: tp.Iterable, total: int, test_features, used_nam
                 continue
             device = estimate.device
             if estimates is None:
-                need = total * 4 * (estimate[0].numel() + output[0].numel()) + total * 8
+                need = total * 4 * (estimate[0].numel() + output[0].numel()) + total * 8 * int(np.prod(label_cols))
                 free = _free_bytes(device)
                 if need > free:
-                    raise NotImplementedError(
-                        f"Not built: a host-memory spill for the test epoch -- the estimates and outputs of {total} "
-                        f"segments take {need} bytes on the device, {free} bytes are free")
+                    raise NotImplementedError(f"Not built: a host-memory spill for {what} of {total} segments take {need} "
+                                              f"bytes on the device, {free} bytes are free")
                 estimates = torch.empty((total,) + tuple(estimate.shape[1:]), device=device, dtype=torch.float32)
                 outputs = torch.empty((total,) + tuple(output.shape[1:]), device=device, dtype=torch.float32)
-                hashes = torch.empty(total, device=device, dtype=torch.int64)
-                flag = word_hash_flag(device)
-                flag.zero_()                                # bits an epoch that ended in an exception left behind
+                labels = torch.empty((total,) + label_cols, device=device, dtype=torch.int64)
+                flag(device).zero_()
             m = estimate.shape[0]
             if n + m > total:
-                raise ValueError(f"collect_wer: the loader delivers more than the announced {total} segments")
+                raise ValueError(f"collect_{name}: the loader delivers more than the announced {total} segments")
             estimates[n:n + m].copy_(estimate)
             outputs[n:n + m].copy_(output)
-            H.word_hash_pick(batch.features, channel, check_at_time, reject_mask.to(device), hashes, n, flag, count=m)
+            launch(batch, k, reject_mask.to(device), labels, n, m)
             n += m
     solver.check_pending_flags()
     if n == 0:
-        raise RuntimeError("wer_epoch: every test segment was rejected (bm/wer.py:67 would concatenate an empty list)")
-    raise_if_word_hash_error(hashes.device)
-    return estimates[:n], outputs[:n], hashes[:n]
+        raise RuntimeError(f"{name}_epoch: every test segment was rejected ({cite} would concatenate an empty list)")
+    return estimates[:n], outputs[:n], labels[:n]
+
+
+def collect_wer(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str],
+                check_at_time: int) -> tp.Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """bm/wer.py:24-25, 47-69, the collection loop: ``(estimates [n, ...], outputs [n, ...], word_hashes [n] int64)`` of
+    the kept segments of ``loader``'s device batches (at most ``total`` segments), all three views of resident device
+    arrays.  See ``wer_epoch``, which builds the loader."""
+    channel = test_features.get_slice("WordHash").start
+
+    def launch(batch, k, reject_mask, hashes, n, m):
+        H.word_hash_pick(batch.features, channel, check_at_time, reject_mask, hashes, n, word_hash_flag(hashes.device),
+                         count=m)
+    out = _collect(solver, loader, total, test_features, used_names, name="wer", label_cols=(), flag=word_hash_flag,
+                   launch=launch, what="the test epoch -- the estimates and outputs", cite="bm/wer.py:67")
+    raise_if_word_hash_error(out[2].device)
+    return out
 
 
 def wer_from_loader(solver, loader: tp.Iterable, total: int, test_features, used_names: tp.Sequence[str],
@@ -259,6 +262,39 @@ def wer_from_loader(solver, loader: tp.Iterable, total: int, test_features, used
     estimates, outputs, hashes = collect_wer(solver, loader, total, test_features, used_names, check_at_time)
     return get_wer(solver.loss, estimates, outputs, hashes, n_negatives=wer_negatives, topx=wer_topx,
                    generator=negatives_generator, wer_random=wer_random)
+
+
+def _epoch_prologue(who: str, segments, test_features, used_names: tp.Sequence[str], n_recordings: tp.Optional[int],
+                    study: tp.Optional[str], tmin: tp.Optional[float], batch_size: int,
+                    shape_check: tp.Callable[[tp.Tuple[int, int, int], int, int, int], None], *,
+                    own_checks: tp.Callable[[], None] = lambda: None,
+                    segment_checks: tp.Callable[[tp.Any], None] = lambda segments: None, rank_note: str = "",
+                    empty_note: str = ""):
+    """What ``wer_epoch`` and ``segment_eval_epoch`` (``who``) check and derive before they build their loader, in the
+    order in which they raise: one rank; ``own_checks()``; the builder describes the segments' channels and holds the
+    used features; the picked recordings (``wer_segments``); ``segment_checks(picked segments)``; ``check_at_time`` from
+    ``tmin`` (`dset.test.tmin`, by default the segments' own); the label launch's ``shape_check(batch shape, WordHash
+    channel, check_at_time, total)``; a test set that is not empty.  Returns ``(used_names, segments, total,
+    check_at_time)``."""
+    if distrib.world_size() > 1:
+        raise NotImplementedError(f"Not built: {who} in a process group of more than one rank{rank_note}")
+    own_checks()
+    if segments.n_features != test_features.dimension:
+        raise ValueError(f"the segments carry {segments.n_features} feature channels, test_features describes "
+                         f"{test_features.dimension}")
+    used_names = list(used_names)
+    assert all([name in test_features for name in used_names])          # bm/features/base.py:152
+    channel = test_features.get_slice("WordHash").start
+    segments = wer_segments(segments, n_recordings, study)
+    total = len(segments)
+    segment_checks(segments)
+    if tmin is None:
+        tmin = segments.tmin
+    t0 = check_at_time(tmin, segments.sample_rate)
+    shape_check((batch_size, test_features.dimension, segments.T), channel, t0, total)
+    if total == 0:
+        raise RuntimeError(f"{who}: no test segment{empty_note}")
+    return used_names, segments, total, t0
 
 
 def wer_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, batch_size: int,
@@ -286,27 +322,16 @@ def wer_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, 
     hashes below 2^24 in magnitude (``WordHash(buckets=...)``).  Not built (``NotImplementedError``): more than one
     rank (the reference shards the loader and averages the metrics), test sets whose two arrays do not fit on the
     card (no host-memory spill); the soft WER is not computed."""
-    if distrib.world_size() > 1:
-        raise NotImplementedError("Not built: wer_epoch in a process group of more than one rank (the reference shards "
-                                  "the test loader over the ranks and averages the metrics, bm/wer.py:37, 121)")
-    if not isinstance(solver.loss, ClipLoss):
-        raise AssertionError(f"wer_epoch ranks with ClipLoss (bm/wer.py:87), the solver's loss is "
-                             f"{type(solver.loss).__name__}")
+    def clip_loss():
+        if not isinstance(solver.loss, ClipLoss):
+            raise AssertionError(f"wer_epoch ranks with ClipLoss (bm/wer.py:87), the solver's loss is "
+                                 f"{type(solver.loss).__name__}")
+    used_names, segments, total, t0 = _epoch_prologue(
+        "wer_epoch", segments, test_features, used_names, wer_recordings, wer_study, tmin, batch_size,
+        lambda shape, channel, t0, total: H.word_hash_pick_check(shape, channel, t0, total, 0, 0), own_checks=clip_loss,
+        rank_note=" (the reference shards the test loader over the ranks and averages the metrics, bm/wer.py:37, 121)",
+        empty_note=" (bm/wer.py:67 would concatenate an empty list)")
     from .dataset import DeviceSegmentLoader
-    if segments.n_features != test_features.dimension:
-        raise ValueError(f"the segments carry {segments.n_features} feature channels, test_features describes "
-                         f"{test_features.dimension}")
-    used_names = list(used_names)
-    assert all([name in test_features for name in used_names])          # bm/features/base.py:152
-    channel = test_features.get_slice("WordHash").start
-    segments = wer_segments(segments, wer_recordings, wer_study)
-    total = len(segments)
-    if tmin is None:
-        tmin = segments.tmin
-    t0 = check_at_time(tmin, segments.sample_rate)
-    H.word_hash_pick_check((batch_size, test_features.dimension, segments.T), channel, t0, total, 0, 0)
-    if total == 0:
-        raise RuntimeError("wer_epoch: no test segment (bm/wer.py:67 would concatenate an empty list)")
     loader = DeviceSegmentLoader(segments, batch_size, shuffle=True, generator=generator)
     return wer_from_loader(solver, loader, total, test_features, used_names, t0, wer_negatives=wer_negatives,
                            wer_topx=wer_topx, wer_random=wer_random, negatives_generator=negatives_generator)
@@ -320,25 +345,12 @@ METADATA_KEYS = ("word_hashes", "word_indices", "seq_indices", "segment_hashes",
 
 # One flag word per device for the evaluation's labels and the first occurrences (hip_ops.SEGMENT_EVAL_*_BIT,
 # FIRST_OCCURRENCE_RANGE_BIT), owned by this module.  Read once per evaluation, after the first-occurrence launches.
-_segment_eval_flags: tp.Dict[torch.device, torch.Tensor] = {}
-
-
-def segment_eval_flag(device) -> torch.Tensor:
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    flag = _segment_eval_flags.get(device)
-    if flag is None:
-        flag = _segment_eval_flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
-    return flag
+segment_eval_flag = H.DeviceFlag()
 
 
 def raise_if_segment_eval_error(device) -> None:
     """Synchronising check of the flag, which it clears."""
-    flag = segment_eval_flag(device)
-    bits = int(flag.item())
-    if bits:
-        flag.zero_()
+    bits = segment_eval_flag.take(device)
     if bits & H.SEGMENT_EVAL_VALUE_BIT:
         raise AssertionError("a word hash (scripts/run_eval_probs.py:116-130) is not finite, not an integer or not below "
                              "2^63 in magnitude")
@@ -379,51 +391,19 @@ def collect_segment_eval(solver, loader, total: int, test_features, used_names: 
     """The loop of ``_load_test_data`` (scripts/run_eval_probs.py:95-158) over a ``DeviceSegmentLoader``: ``(preds [n,
     ...], trues [n, ...], labels [n, 7] int64)`` of the kept segments, views of resident device arrays; the structure of
     ``collect_wer``.  ``trues`` is every kept row's output: the de-duplication happens once, over the epoch."""
-    used_names = list(used_names)
     segments = loader.segments
     channel = test_features.get_slice("WordHash").start
     word_kind = segments.builder.kinds.index(WORD_KIND)
     events = segments.tables()[1]
-    for model in solver._all_models():
-        model.train(False)
-    solver.loss.train(False)
-    preds = trues = labels = None
-    flag = segment_eval_flag(segments.device)
-    flag.zero_()                                            # bits an evaluation that ended in an exception left behind
-    n = 0
-    with torch.no_grad():
-        for k, batch in enumerate(loader):
-            features = test_features.extract_features(batch.features, used_names)
-            estimate, output, _, reject_mask = solver._process_batch(batch.replace(features=features))
-            if getattr(solver, "_gather", None) is not None and solver.feature_model is None:
-                solver._gather.wait()
-            if estimate is None:
-                continue
-            device = estimate.device
-            if preds is None:
-                need = total * 4 * (estimate[0].numel() + output[0].numel()) + total * 8 * len(METADATA_KEYS)
-                free = _free_bytes(device)
-                if need > free:
-                    raise NotImplementedError(
-                        f"Not built: a host-memory spill for the segment-level evaluation -- the predictions, outputs "
-                        f"and labels of {total} segments take {need} bytes on the device, {free} bytes are free")
-                preds = torch.empty((total,) + tuple(estimate.shape[1:]), device=device, dtype=torch.float32)
-                trues = torch.empty((total,) + tuple(output.shape[1:]), device=device, dtype=torch.float32)
-                labels = torch.empty(total, len(METADATA_KEYS), device=device, dtype=torch.int64)
-            m = estimate.shape[0]
-            if n + m > total:
-                raise ValueError(f"collect_segment_eval: the loader delivers more than the announced {total} segments")
-            preds[n:n + m].copy_(estimate)
-            trues[n:n + m].copy_(output)
-            H.segment_eval_labels(batch.features, channel, check_at_time, reject_mask.to(device), loader.epoch_arrays,
-                                  k * loader.batch_size, events, word_kind, infos, segments.sample_rate, labels, n, flag,
-                                  count=m)
-            n += m
-    solver.check_pending_flags()
-    if n == 0:
-        raise RuntimeError("segment_eval_epoch: every test segment was rejected (scripts/run_eval_probs.py:179 would "
-                           "concatenate an empty list)")
-    return preds[:n], trues[:n], labels[:n]
+
+    def launch(batch, k, reject_mask, labels, n, m):
+        H.segment_eval_labels(batch.features, channel, check_at_time, reject_mask, loader.epoch_arrays,
+                              k * loader.batch_size, events, word_kind, infos, segments.sample_rate, labels, n,
+                              segment_eval_flag(labels.device), count=m)
+    return _collect(solver, loader, total, test_features, used_names, name="segment_eval",
+                    label_cols=(len(METADATA_KEYS),), flag=segment_eval_flag, launch=launch,
+                    what="the segment-level evaluation -- the predictions, outputs and labels",
+                    cite="scripts/run_eval_probs.py:179")
 
 
 def segment_eval_epoch(solver, segments, test_features, used_names: tp.Sequence[str], *, batch_size: int,
@@ -466,33 +446,24 @@ def segment_eval_epoch(solver, segments, test_features, used_names: tp.Sequence[
     ``recording_id`` let a caller look them up), the reference's fallback that hashes the word strings when the
     builder has no ``WordHash`` (``ValueError``), the files on disk, ``Evaluator`` / ``EvalJob`` / submitit, more than
     one rank and a host-memory spill (``NotImplementedError``)."""
-    if distrib.world_size() > 1:
-        raise NotImplementedError("Not built: segment_eval_epoch in a process group of more than one rank")
-    if "WordHash" not in test_features:
-        raise ValueError("segment_eval_epoch: the features builder has no WordHash; the reference's fallback that hashes "
-                         "the word strings (scripts/run_eval_probs.py:110-113) is not built")
-    if getattr(segments, "builder", None) is None:
-        raise ValueError("segment_eval_epoch: the segments carry no events (full-length feature arrays hold no words)")
-    if segments.n_features != test_features.dimension:
-        raise ValueError(f"the segments carry {segments.n_features} feature channels, test_features describes "
-                         f"{test_features.dimension}")
-    used_names = list(used_names)
-    assert all([name in test_features for name in used_names])          # bm/features/base.py:152
-    channel = test_features.get_slice("WordHash").start
-    segments = wer_segments(segments, n_recordings, test_study)
-    total = len(segments)
-    evaluated = sorted(set(int(r) for r in segments.rec))
-    for r in evaluated:
-        if segments.recordings[r].events.word_info_host is None:
-            raise ValueError(f"segment_eval_epoch: the word events of recording {r} carry no word_index / sequence_id "
-                             "columns (features.DeviceEvents)")
-    if tmin is None:
-        tmin = segments.tmin
-    t0 = check_at_time(tmin, segments.sample_rate)
-    H.segment_eval_labels_check((batch_size, test_features.dimension, segments.T), channel, t0,
-                                (total, len(METADATA_KEYS)), 0, 0)
-    if total == 0:
-        raise RuntimeError("segment_eval_epoch: no test segment")
+    def has_words():
+        if "WordHash" not in test_features:
+            raise ValueError("segment_eval_epoch: the features builder has no WordHash; the reference's fallback that "
+                             "hashes the word strings (scripts/run_eval_probs.py:110-113) is not built")
+        if getattr(segments, "builder", None) is None:
+            raise ValueError("segment_eval_epoch: the segments carry no events (full-length feature arrays hold no words)")
+
+    def has_word_info(picked):
+        for r in sorted(set(int(r) for r in picked.rec)):
+            if picked.recordings[r].events.word_info_host is None:
+                raise ValueError(f"segment_eval_epoch: the word events of recording {r} carry no word_index / "
+                                 "sequence_id columns (features.DeviceEvents)")
+    used_names, segments, total, t0 = _epoch_prologue(
+        "segment_eval_epoch", segments, test_features, used_names, n_recordings, test_study, tmin, batch_size,
+        lambda shape, channel, t0, total: H.segment_eval_labels_check(shape, channel, t0, (total, len(METADATA_KEYS)),
+                                                                      0, 0),
+        own_checks=has_words, segment_checks=has_word_info)
+    evaluated = set(int(r) for r in segments.rec)
     clip_loss = solver.loss if isinstance(solver.loss, ClipLoss) else ClipLoss(**dict(clip or {})).to(segments.device)
     from .dataset import DeviceSegmentLoader
     rows, n_ids = dense_segment_ids([segments.recordings[r].events.word_info_host if r in evaluated else None

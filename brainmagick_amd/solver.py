@@ -593,11 +593,15 @@ class Solver:
                                "re-runs the last good batch in its place, bm/solver.py:345-352)")
         return loss
 
-    def _eval_loss(self, batch) -> tp.Optional[torch.Tensor]:
-        """The body of ``eval_step`` (the caller holds ``no_grad``); None: the batch was fully rejected."""
+    def _eval_mode(self) -> None:
+        """The models and the loss in eval mode (a ClipLoss trims by its training windows only in train mode)."""
         for m in self._all_models():
             m.train(False)
         self.loss.train(False)
+
+    def _eval_loss(self, batch) -> tp.Optional[torch.Tensor]:
+        """The body of ``eval_step`` (the caller holds ``no_grad``); None: the batch was fully rejected."""
+        self._eval_mode()
         estimate, output, features_mask, _, limit = self._forward(batch, training=False)
         if estimate is None:
             return None

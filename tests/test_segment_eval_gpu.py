@@ -332,6 +332,77 @@ def test_first_occurrence_out_of_range_leaves_the_other_rows_right(H):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The collection loop over the batches the reference ran (tests/golden/segment_eval.npz)
+# ---------------------------------------------------------------------------------------------------------------------
+class CannedEpoch:
+    """The stand-ins of the fixture's maker on the device, for ``collect_segment_eval``: the solver (``_process_batch``
+    returns the recorded estimate and output of the kept rows), and the loader with the segments it belongs to (the
+    fixture's batches in order, the epoch's arrays and the word tables)."""
+    feature_model = None
+    _gather = None
+
+    def __init__(self, H, meta, case):
+        from brainmagick_amd.losses import ClipLoss
+        from brainmagick_amd.synthetic import SegmentBatch
+        self.loss = ClipLoss().cuda()
+        words = Tables(H, case["tables"])
+        self.builder, self.sample_rate, self.device = words.builder, meta["sample_rate"], torch.device("cuda", 0)
+        self.tables = lambda: (None, words.table)
+        self.infos = words.infos
+        self.segments, self.batch_size = self, meta["batch_size"]
+        self.epoch_arrays = epoch_arrays(*(np.concatenate([b[k] for b in case["batches"]])
+                                           for k in ("rec", "wstart", "subject", "recording")))
+        self.by_id, self.batches = {}, []
+        for b in case["batches"]:
+            B = len(b["keep"])
+            batch = SegmentBatch(torch.zeros(B, 1, T, device="cuda"), torch.from_numpy(b["features"].copy()).cuda(),
+                                 torch.ones(B, 1, T, dtype=torch.bool, device="cuda"),
+                                 torch.zeros(B, dtype=torch.int64, device="cuda"),
+                                 torch.zeros(B, dtype=torch.int64, device="cuda"))
+            self.by_id[id(batch.meg)] = b
+            self.batches.append(batch)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+    def _all_models(self):
+        return []
+
+    def check_pending_flags(self):
+        pass
+
+    def _process_batch(self, batch):
+        b = self.by_id[id(batch.meg)]
+        keep = torch.from_numpy(b["keep"]).cuda()
+        if b["estimate"] is None:
+            return None, None, None, keep
+        return (torch.from_numpy(b["estimate"]).cuda(), torch.from_numpy(b["output"]).cuda(), batch.features_mask[keep],
+                keep)
+
+
+def test_bits_left_by_an_aborted_evaluation_do_not_reach_the_next(H, golden):
+    """The flag word is the module's: an evaluation that ended in an exception never read it; the next collection
+    starts clean, and its labels are the ones the reference's ``_load_test_data`` collected."""
+    from brainmagick_amd import retrieval
+    meta, name = golden.meta, "t0_6"
+    c = meta["cases"][name]
+    epoch = CannedEpoch(H, meta, SC.fixture_case(golden.raw, meta, name))
+    specs = [FC.feature(f, "constant", "word", cardinality=meta["cardinality"][f]) for f in meta["features"]]
+    retrieval.segment_eval_flag("cuda").fill_(15)
+    preds, trues, labels = retrieval.collect_segment_eval(epoch, epoch, sum(c["batches"]),
+                                                          FC.make_builder(specs, meta["sample_rate"]), c["names"],
+                                                          c["check_at_time"], epoch.infos)
+    assert int(retrieval.segment_eval_flag("cuda").item()) == 0
+    got = labels.cpu().numpy()
+    assert got.shape == (c["n_kept"], 7) and labels.dtype == torch.int64
+    for column, key in ((0, "word_hashes"), (1, "word_indices"), (2, "seq_indices"), (4, "subject_id"), (5, "recording_id")):
+        assert np.array_equal(got[:, column], golden.raw[f"{name}/{key}"]), key
+    assert np.array_equal(SC.groups(got[:, 3]), golden.raw[f"{name}/segment_groups"])
+    assert np.array_equal(preds.cpu().numpy(), golden.raw[f"{name}/estimate"])
+    assert np.array_equal(trues.cpu().numpy(), golden.raw[f"{name}/output"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # End to end over resident segments
 # ---------------------------------------------------------------------------------------------------------------------
 N_SAMPLES = 1300
@@ -538,6 +609,16 @@ def test_segments_without_word_information_are_refused(epoch):
     from brainmagick_amd import retrieval
     with pytest.raises(ValueError, match="word_index / sequence_id"):
         retrieval.segment_eval_epoch(make_solver(), seg, builder, ["Mel"], batch_size=7)
+
+
+def test_not_built_host_spill_names_the_bytes(epoch, monkeypatch):
+    """The labels are part of what has to fit: 7 int64 per row, next to the two fp32 arrays."""
+    from brainmagick_amd import retrieval
+    monkeypatch.setattr(retrieval, "_free_bytes", lambda device: 1000)
+    n = len(epoch["seg"])
+    need = n * 4 * (8 * 37 + 8 * 37) + n * 8 * 7
+    with pytest.raises(NotImplementedError, match=f"Not built.*{need} bytes.*1000 bytes"):
+        run_eval(epoch)
 
 
 def test_solver_segment_eval_is_pure_dispatch(epoch, monkeypatch):
